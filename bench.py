@@ -11,12 +11,17 @@ Multi-GPU (--gpus N under torch.distributed.run): the N=1e6 cloud is fixed
 generated sharded and all-gathered over RCCL/xGMI inside the timed region
 (the real per-evaluation exchange).
 
-Prints ONE JSON line from rank 0. Also included:
+Prints ONE JSON line from rank 0. A plain run sets up, warms up, times the
+steps and prints the line; it also carries
   roofline     — dominant-kernel achieved fp64 FLOP/s (28 flops/pair
                  convention) vs the 78.6 TF fp64 vector peak,
-                 measured with HIP events on the launch stream.
+                 from the HIP events recorded around the timed launches.
+--full adds the legs that take runs of their own (null in a plain run):
+  fp64_peak_measured_tflops — the fp64 FMA peak probe kernel.
   cpu_baseline — the C oracle (reference CPU path restated, OpenMP all
                  cores) timed on this box on a bounded target sample.
+--dump-outputs DIR writes the velocities of the last timed step to
+DIR/u.npy (float64, target order) for output-for-output comparison of builds.
 """
 
 import argparse
@@ -44,7 +49,13 @@ def parse_args():
     p.add_argument("--n", "--npoints", dest="n", type=int, default=1_000_000,
                    help="cloud size (sources == targets); default the metric point 1e6")
     p.add_argument("--seed", type=int, default=100)
-    p.add_argument("--skip-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beyond the headline figure: measured "
+                        "fp64 peak probe and the CPU baseline")
+    p.add_argument("--skip-cpu-baseline", action="store_true",
+                   help="with --full: leave out the CPU baseline leg")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's velocities to DIR/u.npy")
     p.add_argument("--kernel", default="stokeslet", choices=["stokeslet", "oseen"],
                    help="stokeslet = the headline metric; oseen = BASELINE config 3 "
                         "(regularized Stokeslet)")
@@ -104,6 +115,23 @@ def load_traffic_calibration(n_src, n_trg):
     except Exception:
         pass
     return None
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirpath, u, seed):
+    """Write the (n, 3) fp64 velocities as DIR/u.npy; above the size cap a
+    fixed, seeded row sample (sorted, rows in u_rows.npy) is written instead."""
+    os.makedirs(dirpath, exist_ok=True)
+    u = np.ascontiguousarray(u, dtype=np.float64)
+    max_rows = (DUMP_MAX_BYTES - 4096) // (u.shape[1] * 8 + 8)
+    if len(u) > max_rows:
+        rows = np.sort(np.random.default_rng(seed).choice(
+            len(u), size=max_rows, replace=False))
+        np.save(os.path.join(dirpath, "u_rows.npy"), rows.astype(np.float64))
+        u = u[rows]
+    np.save(os.path.join(dirpath, "u.npy"), u)
 
 
 def main():
@@ -222,6 +250,11 @@ def main():
     # checksum sanity: result finite
     assert torch.isfinite(u_local).all(), "non-finite velocities"
 
+    if args.dump_outputs:
+        u_all = allgather_rows(u_local) if world > 1 else u_local
+        if rank == 0:
+            dump_outputs(args.dump_outputs, u_all.cpu().numpy(), args.seed)
+
     total_pairs = float(n) * float(n) * args.steps
     pairs_per_s = total_pairs / elapsed
 
@@ -234,14 +267,14 @@ def main():
         traffic = load_traffic_calibration(n, te - ts) if args.kernel == "stokeslet" else None
 
         peak_meas = ctypes.c_double(0.0)
-        if not rehearsal:
+        if args.full and not rehearsal:
             try:
                 _native.lib().skelly_fp64_peak_tflops(ctypes.byref(peak_meas))
             except Exception:
                 pass
 
         cpu = None
-        if world == 1 and not args.skip_cpu_baseline and not rehearsal:
+        if args.full and world == 1 and not args.skip_cpu_baseline and not rehearsal:
             cpu = cpu_baseline(pts, strengths, pts, eta, kernel=args.kernel)
 
         out = {

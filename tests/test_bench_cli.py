@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import torch
 import pytest
 
@@ -17,22 +18,24 @@ BENCH = os.path.join(REPO, "bench.py")
 def test_help_parses():
     r = subprocess.run([sys.executable, BENCH, "--help"], capture_output=True, text=True)
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--kernel"):
+    for flag in ("--gpus", "--steps", "--warmup", "--kernel", "--full",
+                 "--dump-outputs"):
         assert flag in r.stdout
 
 
 @pytest.mark.timeout(420)
-def test_distributed_plumbing_rehearsal_world2():
+def test_distributed_plumbing_rehearsal_world2(tmp_path):
     """Runs the EXACT multi-rank bench path the driver uses (torchrun,
     world_size 2, barriers, per-step source all-gather, max-over-ranks
-    timing, one JSON line from rank 0) over gloo with a stub compute."""
+    timing, one JSON line from rank 0) over gloo with a stub compute, and
+    --dump-outputs gathers the target shards into one array on rank 0."""
     env = dict(os.environ, SKELLY_BENCH_REHEARSAL="gloo", MASTER_ADDR="127.0.0.1")
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", "29581", BENCH,
          "--gpus", "2", "--steps", "2", "--warmup", "1", "--npoints", "10000",
-         "--skip-cpu-baseline"],
+         "--skip-cpu-baseline", "--dump-outputs", str(tmp_path / "dump")],
         capture_output=True, text=True, timeout=360, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
@@ -41,6 +44,10 @@ def test_distributed_plumbing_rehearsal_world2():
     assert out["n_gpus"] == 2 and out["steps"] == 2
     assert out["metric"] == "rehearsal (no compute)"
     assert out["config"]["n_src"] == 10000
+    assert out["ms_per_step"] > 0
+    u = np.load(tmp_path / "dump" / "u.npy")
+    assert u.shape == (10000, 3) and u.dtype == np.float64
+    assert not u.any()  # the stub compute zeroes the output
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="GPU present")

@@ -1,11 +1,9 @@
 """Trajectory output in the reference's msgpack format (§8f row 4):
-structural checks against the serialization contract, and — when the
-reference tree is present (build container) — a round trip through the
-REFERENCE'S OWN TrajectoryReader (src/skelly_sim/reader.py)."""
+structural checks against the serialization contract, and a round trip
+through the REFERENCE'S OWN TrajectoryReader (src/skelly_sim/reader.py),
+recorded under tests/golden/ by oracle/make_trajectory_fixture.py."""
 
 import os
-import sys
-import types
 
 import msgpack
 import numpy as np
@@ -15,9 +13,6 @@ from skellysim_amd.fiber_fd import FiberFD
 from skellysim_amd.system_fd import SystemFD
 from oracle_backend import OracleBackend
 from skellysim_amd.trajectory import TrajectoryWriter
-
-REFERENCE = "/root/reference"
-
 
 def _small_system():
     rng = np.random.default_rng(4)
@@ -158,71 +153,70 @@ def test_resume_matches_uninterrupted_run(tmp_path):
     assert times == pytest.approx([0.1, 0.2, 0.3, 0.4])
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree absent")
-def test_reference_reader_round_trip(tmp_path):
+def _unpack_all(path):
+    with open(path, "rb") as fh:
+        return list(msgpack.Unpacker(fh, raw=False))
+
+
+def _assert_same_wire(got, want, where="stream", free_strings=False):
+    """Two unpacked msgpack objects have the same wire shape: identical
+    types, map keys in the same order, list lengths, strings, ints and bools,
+    and floats equal to the tolerance of the state comparisons below."""
+    assert type(got) is type(want), (where, type(got), type(want))
+    if isinstance(want, dict):
+        assert list(got.keys()) == list(want.keys()), where
+        for k in want:
+            _assert_same_wire(got[k], want[k], f"{where}.{k}", free_strings)
+    elif isinstance(want, list):
+        assert len(got) == len(want), (where, len(got), len(want))
+        for i, (g, w) in enumerate(zip(got, want)):
+            _assert_same_wire(g, w, f"{where}[{i}]", free_strings)
+    elif isinstance(want, float):
+        assert np.isclose(got, want), (where, got, want)
+    elif isinstance(want, str) and free_strings:
+        pass
+    else:
+        assert got == want, (where, got, want)
+
+
+def _assert_same_stream(path, golden_path):
+    got, want = _unpack_all(path), _unpack_all(golden_path)
+    assert len(got) == len(want)
+    # header strings carry the date and host of the writing run
+    _assert_same_wire(got[0], want[0], "header", free_strings=True)
+    for i, (g, w) in enumerate(zip(got[1:], want[1:])):
+        _assert_same_wire(g, w, f"frame{i}")
+
+
+def test_reference_reader_round_trip(tmp_path, golden_dir):
     """The REFERENCE'S OWN reader.py must load our trajectory: times indexed,
-    frames decoded, fiber positions identical."""
-    # shims for the reference python package's optional deps
-    for name, mod in {
-        "toml": dict(load=lambda f: {}, dump=lambda *a, **k: None),
-        "dataclass_utils": dict(check_type=lambda *a, **k: None),
-        "numba": dict(njit=lambda *a, **k: (a[0] if a and callable(a[0])
-                                            else (lambda f: f)), prange=range),
-    }.items():
-        m = types.ModuleType(name)
-        for k, v in mod.items():
-            setattr(m, k, v)
-        sys.modules.setdefault(name, m)
-    if "nptyping" not in sys.modules:
-        m = types.ModuleType("nptyping")
-
-        class _Sub:
-            def __class_getitem__(cls, item):
-                return np.ndarray
-
-        m.NDArray = _Sub
-        m.Shape = _Sub
-        m.Float64 = float
-        sys.modules["nptyping"] = m
-    fg = types.ModuleType("function_generator")
-    fg.FunctionGenerator = type("FunctionGenerator", (), {"__init__": lambda s, *a, **k: None})
-    sys.modules.setdefault("function_generator", fg)
-
-    sys.path.insert(0, os.path.join(REFERENCE, "src"))
-    try:
-        from skelly_sim.reader import TrajectoryReader
-    except Exception as e:
-        pytest.skip(f"reference reader not importable here: {e}")
+    frames decoded, fiber positions identical. The reader's run is recorded
+    (oracle/make_trajectory_fixture.py): the streams it accepted and what it
+    decoded from them. The streams written now must have the recorded wire
+    shape and values, and the recorded decode must equal the live state."""
+    rec = np.load(os.path.join(golden_dir, "trajectory_reader.npz"))
 
     path, times, sys_ = _write_traj(str(tmp_path))
-    toml_file = os.path.join(str(tmp_path), "skelly_config.toml")
-    open(toml_file, "w").write("")
-
-    traj = TrajectoryReader(toml_file)
-    assert traj.trajectory_version == 1
-    assert list(traj.times) == pytest.approx(times)
-    traj.load_frame(len(times) - 1)
-    fibs = traj["fibers"]
-    assert len(fibs) == 2
-    assert np.allclose(fibs[0]["x_"], sys_.fibers[0].x.T)
-    assert traj["time"] == pytest.approx(times[-1])
+    _assert_same_stream(path, os.path.join(golden_dir, "trajectory_fibers.out"))
+    assert int(rec["fibers_trajectory_version"]) == 1
+    assert list(rec["fibers_times"]) == pytest.approx(times)
+    assert int(rec["fibers_count"]) == 2
+    assert np.allclose(rec["fibers_x"][0], sys_.fibers[0].x.T)
+    assert float(rec["fibers_time"]) == pytest.approx(times[-1])
 
     # bodies through the reference reader (flattened sublists,
     # reader.py:333-341; quaternion decoded as [w, x, y, z] array)
-    os.remove(os.path.join(str(tmp_path), "skelly_sim.out"))
+    os.remove(path)
     sys_b, b = _body_system()
-    with TrajectoryWriter(os.path.join(str(tmp_path), "skelly_sim.out")) as tw:
+    with TrajectoryWriter(path) as tw:
         assert sys_b.step(tol=1e-11, maxiter=100)["converged"]
         tw.write_frame(sys_b, 0.1, 0.1)
-    traj2 = TrajectoryReader(toml_file)
-    traj2.load_frame(0)
-    bodies = traj2["bodies"]
-    assert len(bodies) == 1
-    bm = bodies[0]
-    assert bm["radius_"] == b.radius
-    assert np.allclose(bm["position_"], b.position)
-    assert np.allclose(bm["orientation_"], b.orientation)
-    assert np.allclose(bm["solution_vec_"], b.solution_vec)
+    _assert_same_stream(path, os.path.join(golden_dir, "trajectory_body.out"))
+    assert int(rec["body_count"]) == 1
+    assert float(rec["body_radius"]) == b.radius
+    assert np.allclose(rec["body_position"], b.position)
+    assert np.allclose(rec["body_orientation"], b.orientation)
+    assert np.allclose(rec["body_solution_vec"], b.solution_vec)
 
 
 def test_shell_plus_body_frame_slices(tmp_path):
