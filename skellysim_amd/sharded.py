@@ -17,6 +17,10 @@ The collective logic is backend-agnostic so the world_size>1 path is covered
 by gloo CPU tests (tests/test_sharding.py); compute on the product path is
 the HIP extension (compute_fn defaults to the stokeslet device kernel and
 fails loudly without a GPU).
+
+Comm is the one place that asks torch.distributed whether there is a world:
+the evaluator here and the solve pipeline (system_fd.py / system_dist.py)
+reach their collectives through it.
 """
 
 import numpy as np
@@ -62,6 +66,67 @@ def allgather_rows(local, group=None):
     return torch.cat(parts, dim=0)
 
 
+class Comm:
+    """The questions the solve pipeline asks of torch.distributed — rank,
+    world size, gather rows in rank order, take rank 0's vector, sum over
+    ranks. Every one is the identity when no process group exists or the
+    world is 1, and always for Comm(single=True) (a single-rank system
+    inside somebody else's process group)."""
+
+    def __init__(self, group=None, single=False):
+        self.group = group
+        self.single = single
+
+    def _dist(self):
+        """torch.distributed if there is a process group to talk to."""
+        import torch.distributed as dist
+        if not self.single and dist.is_available() and dist.is_initialized():
+            return dist
+        return None
+
+    @property
+    def world(self):
+        dist = self._dist()
+        return dist.get_world_size(self.group) if dist else 1
+
+    @property
+    def rank(self):
+        dist = self._dist()
+        return dist.get_rank(self.group) if dist else 0
+
+    def gather_rows(self, a):
+        """All ranks' (n_local, ...) rows, rank 0's first (allgather_rows);
+        numpy array or tensor in, the same kind out."""
+        import torch
+        if self.world == 1:
+            return a
+        if torch.is_tensor(a):
+            return allgather_rows(a, self.group)
+        t = torch.from_numpy(np.ascontiguousarray(a).reshape(
+            len(a), int(np.prod(a.shape[1:]))))
+        return allgather_rows(t, self.group).numpy().reshape(-1, *a.shape[1:])
+
+    def from_root(self, a, n):
+        """Rank 0's length-n fp64 numpy vector a on every rank (a is
+        ignored on the other ranks)."""
+        import torch
+        if self.world == 1:
+            return a
+        t = torch.from_numpy(np.array(a, float) if self.rank == 0
+                             else np.zeros(n))
+        self._dist().broadcast(t, src=0, group=self.group)
+        return t.numpy()
+
+    def sum(self, a):
+        """Elementwise sum of a numpy array over ranks."""
+        import torch
+        if self.world == 1:
+            return a
+        t = torch.from_numpy(np.array(a))
+        self._dist().all_reduce(t, group=self.group)
+        return t.numpy()
+
+
 class ShardedPairEvaluator:
     """Target-sharded pair evaluation over a torch.distributed world.
 
@@ -87,16 +152,11 @@ class ShardedPairEvaluator:
                 raise ValueError(f"unknown kernel {kernel!r}")
 
         self._compute = compute_fn
-        self._group = group
+        self._comm = Comm(group)
 
     def __call__(self, r_src_local, f_src_local, r_trg_local, eta=1.0):
-        import torch.distributed as dist
-
-        if dist.is_available() and dist.is_initialized():
-            r_all = allgather_rows(r_src_local, self._group)
-            f_all = allgather_rows(f_src_local, self._group)
-        else:
-            r_all, f_all = r_src_local, f_src_local
+        r_all = self._comm.gather_rows(r_src_local)
+        f_all = self._comm.gather_rows(f_src_local)
         return self._compute(r_all, f_all, r_trg_local, eta)
 
 

@@ -12,32 +12,20 @@ own target block. GMRES runs with distributed inner products
 The reference hard-forbids its direct evaluators under >1 rank
 (system.cpp:618-623); this module is the new multi-GPU capability.
 
-Two iteration paths share the math: a host (numpy) path, and the
-device-resident path (_apply_matvec_device/_apply_precond_device) where the
-whole GMRES iteration — batched fiber blocks, pair kernels, row-block shell
-GEMVs, distributed dot-blocks — runs on device tensors with only the wf /
-shell-density all-gathers per iteration (RCCL over xGMI on GPUs) plus one
-fiber-position gather per solve. Covered by gloo world-2 CPU tests
-(tests/test_dist_system.py; the device layout runs there on CPU tensors with
-oracle-backed kernel fakes) and by a world-1 HIP test (test_gpu_system.py);
-the same code drives RCCL + HIP kernels on multi-GPU boxes.
+There is no second pipeline here: prep, the host and the device-resident
+matvec/preconditioner, solve and step are SystemFD's, which is written
+against a rank-local layout and a communicator (see system_fd.py). This
+module supplies the two things that make a rank's view non-trivial — the
+layout (own shell rows; body block on rank 0 only) and the live
+communicator — so at world size 1 it IS the single-rank solve. Covered by
+gloo world-2 CPU tests (tests/test_dist_system.py; the device layout runs
+there on CPU tensors with oracle-backed kernel fakes) and by a world-1 HIP
+test (test_gpu_system.py); the same code drives RCCL + HIP kernels on
+multi-GPU boxes.
 """
 
-import numpy as np
-import torch
-
-from .sharded import shard_range, allgather_rows
+from .sharded import Comm, shard_range
 from .system_fd import SystemFD
-
-
-def _allgather_np(a):
-    """All-gather a rank-local (n_local, d) numpy array (rank order)."""
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()):
-        return a
-    t = torch.from_numpy(np.ascontiguousarray(a).reshape(len(a), -1))
-    out = allgather_rows(t)
-    return out.numpy().reshape(-1, *a.shape[1:])
 
 
 class DistributedSystemFD(SystemFD):
@@ -46,377 +34,41 @@ class DistributedSystemFD(SystemFD):
     Construct with this rank's OWN fibers and this rank's OWN shell row block
     (shell.A / shell.M_inv hold the (3n_local, 3N_global) row slices;
     shell.nodes/normals hold the GLOBAL shell geometry, shell_rows the
-    [row0, row1) node range owned here).
+    [row0, row1) node range owned here). Requires >= 1 fiber per rank, with
+    uniform discretization for the device-resident iteration.
     """
+
+    # follows the default process group; the identity without one
+    comm = Comm()
 
     def __init__(self, fibers, eta, dt, shell=None, shell_rows=None,
                  background_flow=None, backend=None, bodies=None):
-        # periphery_interaction is deliberately not accepted here: the
-        # repulsion-induced flow would need all-gathered fiber sources in
-        # prep, which this path does not wire yet (round 2)
-        super().__init__(fibers, eta, dt, shell=None,
+        # periphery_interaction is deliberately not accepted here: its
+        # repulsion-induced flow in prep has not been validated against
+        # the single-process solve under a world > 1 yet
+        self.shell_rows = shell_rows  # (a, b) node indices owned by this rank
+        super().__init__(fibers, eta, dt, shell=shell,
                          background_flow=background_flow, backend=backend,
                          bodies=bodies)
-        self.shell = shell
-        self.shell_rows = shell_rows  # (a, b) node indices owned by this rank
-        if shell is not None:
-            self._shell_matvec_rows, self._shell_precond_rows = \
-                self.backend.shell_ops(shell.A, shell.M_inv)
-
-    # Bodies follow the reference's ownership model: the body objects
-    # (geometry) are REPLICATED on every rank — every rank evaluates their
-    # flow — but the body SOLUTION block lives only in rank 0's local
-    # vector and is broadcast per apply (body_container.hpp:99,
-    # system.cpp:309); the link forces each rank computes from its own
-    # fibers are all-reduced (body_container.cpp:131).
-    @staticmethod
-    def _rank():
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized():
-            return dist.get_rank()
-        return 0
-
-    @property
-    def global_body_sol_size(self):
-        return sum(b.solution_size for b in self.bodies)
-
-    @property
-    def body_sol_size(self):
-        return self.global_body_sol_size if self._rank() == 0 else 0
-
-    def _body_sol_slices(self):
-        if self._rank() != 0:
-            return []
-        out, off = [], self.fiber_sol_size + self.shell_sol_size
-        for b in self.bodies:
-            out.append((b, off, off + b.solution_size))
-            off += b.solution_size
-        return out
-
-    def _body_node_slices(self):
-        if self._rank() != 0:
-            return []
-        out, off = [], self.fiber_node_count + self.shell_sol_size // 3
-        for b in self.bodies:
-            out.append((b, off, off + b.n_nodes))
-            off += b.n_nodes
-        return out
-
-    def _bcast_body_solution(self, x):
-        """Rank 0's body block of x -> all ranks (system.cpp:309)."""
-        import torch.distributed as dist
-        full = np.zeros(self.global_body_sol_size)
-        if self._rank() == 0:
-            full[:] = x[self.fiber_sol_size + self.shell_sol_size:]
-        if dist.is_available() and dist.is_initialized() \
-                and dist.get_world_size() > 1:
-            t = torch.from_numpy(full)
-            dist.broadcast(t, src=0)
-            full = t.numpy()
-        return full
 
     # rank-local solution: [own fibers | own shell rows | bodies if rank 0]
-    @property
-    def shell_sol_size(self):
-        if not self.shell:
-            return 0
-        a, b = self.shell_rows
-        return 3 * (b - a)
-
     def _own_shell_nodes(self):
         a, b = self.shell_rows
         return self.shell.nodes[a:b]
 
-    def all_nodes(self):
-        parts = [self.fiber_nodes()]
-        if self.shell:
-            parts.append(self._own_shell_nodes())
-        if self.bodies and self._rank() == 0:
-            parts.append(self.body_nodes())
-        return np.concatenate(parts, axis=0)
+    def _own_bodies(self):
+        # the body objects are replicated on every rank; their solution
+        # block lives only in rank 0's vector (body_container.hpp:99)
+        return self.bodies if self.comm.rank == 0 else []
 
-    def prep_state_for_solver(self):
-        """Identical to the single-rank prep except the shell block is this
-        rank's rows (v_shell slice at its own nodes); the base prep handles
-        the fiber block and (on rank 0) the body rows."""
-        saved_shell = self.shell
-        self.shell = None  # run the fiber+body part of the base prep
-        rhs_base = super().prep_state_for_solver()
-        self.shell = saved_shell
-        if self.shell:
-            fib_sz = self.fiber_sol_size
-            rhs_fib, rhs_body = rhs_base[:fib_sz], rhs_base[fib_sz:]
-            v_sh = np.zeros((self.shell_sol_size // 3, 3))
-            if self.background_flow is not None:
-                v_sh += self.background_flow(self._own_shell_nodes())
-            if self.bodies:
-                ext_ft = np.stack([
-                    np.concatenate([b.external_force_at(self.time),
-                                    b.external_torque])
-                    for b in self.bodies])
-                if np.any(ext_ft):
-                    v_sh += self._body_flow(
-                        self._own_shell_nodes(),
-                        np.zeros(self.global_body_sol_size), ext_ft)
-            self.RHS = np.concatenate([rhs_fib, -v_sh.reshape(-1), rhs_body])
-        else:
-            self.RHS = rhs_base
-        return self.RHS
-
-    def apply_matvec(self, x):
-        """system.cpp:269-324 with all-gathered sources, local targets;
-        body solution broadcast from rank 0, link forces all-reduced."""
-        nf_nodes = self.fiber_node_count
-        sh_nodes = self.shell_sol_size // 3
-        x_fib = x[: self.fiber_sol_size]
-        x_shell_local = x[self.fiber_sol_size:
-                          self.fiber_sol_size + self.shell_sol_size]
-        r_local = self.all_nodes()
-
-        # fiber sources: gather positions + weighted forces from all ranks
-        fw = self._apply_fiber_force(x_fib)
-        if self.fibers:
-            w = np.concatenate([f.quadrature_weights() for f in self.fibers])
-            wf_local = fw * w[:, None]
-            r_fib_local = self.fiber_nodes()
-        else:
-            wf_local = np.zeros((0, 3))
-            r_fib_local = np.zeros((0, 3))
-        r_fib_all = _allgather_np(r_fib_local)
-        wf_all = _allgather_np(wf_local)
-
-        v_all = self.backend.stokeslet(r_fib_all, wf_all, r_local, self.eta) \
-            if len(r_fib_all) else np.zeros_like(r_local)
-        # per-fiber self subtraction on OWN fibers (local targets lead)
-        if self.fibers and self.fibers[0].stokeslet is None:
-            if self._uniform:
-                pts = np.stack([f.x.T for f in self.fibers])
-                G = self.backend.self_stokeslet_batch(pts, self.eta)
-                for f, g in zip(self.fibers, G):
-                    f.stokeslet = g
-            else:
-                # mixed discretizations: per-fiber batches of one (same
-                # fallback as SystemFD._fiber_flow)
-                for f in self.fibers:
-                    f.stokeslet = self.backend.self_stokeslet_batch(
-                        f.x.T[None], self.eta)[0]
-        for f, a, b in self._fiber_node_slices():
-            v_all[a:b] -= (f.stokeslet @ wf_local[a:b].reshape(-1)).reshape(f.n_nodes, 3)
-
-        if self.shell:
-            dens_all = _allgather_np(x_shell_local.reshape(-1, 3))
-            # shell double layer flows to fibers AND (rank 0's) body nodes,
-            # not to itself (system.cpp:302-305,314-316)
-            trg_idx = np.r_[np.arange(nf_nodes),
-                            np.arange(nf_nodes + sh_nodes, len(r_local))]
-            if len(trg_idx):
-                v_all[trg_idx] += self.backend.stresslet_normal_density(
-                    self.shell.nodes, self.shell.normals, dens_all,
-                    r_local[trg_idx], self.eta)
-
-        vel_on_fiber = None
+    def _device_mode(self, requested):
+        # bodies in the device-resident iteration are single-rank only
         if self.bodies:
-            from .body import calculate_link_conditions
-            import torch.distributed as dist
-            x_bodies_global = self._bcast_body_solution(x)
-            body_vels, off = [], 0
-            for b in self.bodies:
-                body_vels.append(
-                    x_bodies_global[off + 3 * b.n_nodes:
-                                    off + b.solution_size])
-                off += b.solution_size
-            body_vels = np.stack(body_vels)
-            vel_on_fiber, body_ft = calculate_link_conditions(
-                self.fibers, x_fib, body_vels, self.bodies)
-            if dist.is_available() and dist.is_initialized() \
-                    and dist.get_world_size() > 1:
-                t = torch.from_numpy(np.ascontiguousarray(body_ft))
-                dist.all_reduce(t)  # sum link F/T over ranks' fibers
-                body_ft = t.numpy()
-            v_all += self._body_flow(r_local, x_bodies_global, body_ft)
-
-        res = np.zeros_like(x)
-        v_fib = v_all[:nf_nodes]
-        for i, ((f, a, b), (_, na, nb)) in enumerate(
-                zip(self._fiber_slices(), self._fiber_node_slices())):
-            vb = vel_on_fiber[i] if vel_on_fiber is not None else None
-            res[a:b] = f.matvec(x_fib[a:b], v_fib[na:nb].T, vb)
-        if self.shell:
-            # row-block GEMV against the GLOBAL density (Allgatherv +
-            # row-distributed dense ops, periphery.cpp:34-47)
-            x_shell_all = dens_all.reshape(-1)
-            v_shell = v_all[nf_nodes: nf_nodes + sh_nodes].reshape(-1)
-            res[self.fiber_sol_size:
-                self.fiber_sol_size + self.shell_sol_size] = \
-                self._shell_matvec_rows(x_shell_all) + v_shell
-        for (b, a, bb), (_, na, nb) in zip(self._body_sol_slices(),
-                                           self._body_node_slices()):
-            res[a:bb] = b.matvec(v_all[na:nb], x[a:bb])
-        return res
-
-    def apply_preconditioner(self, x):
-        res = np.zeros_like(x)
-        x_fib = x[: self.fiber_sol_size]
-        if self.fibers:
-            if self._uniform:
-                if self._fiber_lu_solve is None:
-                    A_batch = np.stack([f.A for f in self.fibers])
-                    self._fiber_lu_solve = self.backend.batched_lu(A_batch)
-                m = 4 * self.fibers[0].n_nodes
-                sol = self._fiber_lu_solve(x_fib.reshape(len(self.fibers), m))
-                res[: self.fiber_sol_size] = sol.reshape(-1)
-            else:
-                # mixed-discretization local block: per-fiber LU solves
-                # (same fallback SystemFD.apply_preconditioner takes)
-                if self._fiber_lu_solve is None:
-                    self._fiber_lu_solve = [
-                        self.backend.batched_lu(f.A[None])
-                        for f in self.fibers]
-                for (f, a, b), solve in zip(self._fiber_slices(),
-                                            self._fiber_lu_solve):
-                    res[a:b] = solve(x_fib[a:b][None])[0]
-        if self.shell:
-            sh = slice(self.fiber_sol_size,
-                       self.fiber_sol_size + self.shell_sol_size)
-            x_shell_all = _allgather_np(x[sh].reshape(-1, 3)).reshape(-1)
-            res[sh] = self._shell_precond_rows(x_shell_all)
-        for b, a, bb in self._body_sol_slices():
-            res[a:bb] = b.apply_preconditioner(x[a:bb])
-        return res
-
-    # ---- device-resident distributed iteration --------------------------
-    @staticmethod
-    def _gather_t(t):
-        """allgather_rows when a world exists, identity otherwise (tensor)."""
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() \
-                and dist.get_world_size() > 1:
-            return allgather_rows(t)
-        return t
-
-    def _build_device_operators(self):
-        """The single-rank builder works unchanged on the rank-local state
-        (all_nodes() is the local override, shell.A/M_inv are the row
-        blocks, shell.nodes/normals the global geometry); add the one
-        solve-static gather: fiber source positions from all ranks."""
-        super()._build_device_operators()
-        self._dev["r_fib_all"] = self._gather_t(self._dev["r_fib"])
-
-    def _apply_matvec_device(self, x):
-        """apply_matvec on device with all-gathered sources, local targets
-        (the host version above, collective for collective: wf + shell
-        density per iteration over RCCL/xGMI; positions once per solve)."""
-        from .evaluator import stokeslet_device, stresslet_device
-        d = self._dev
-        nf, n = d["nf"], d["n"]
-        eta = self.eta
-        nf_nodes = nf * n  # LOCAL fiber nodes (targets); sources are global
-        x_fib = x[: 4 * nf_nodes].reshape(nf, 4 * n)
-        x_shell_local = x[4 * nf_nodes:]
-
-        fw = torch.bmm(d["F"], x_fib.unsqueeze(-1)).squeeze(-1)      # (nf, 3n)
-        fw_nodes = fw.reshape(nf, 3, n).permute(0, 2, 1).reshape(nf_nodes, 3)
-        wf = (fw_nodes * d["w"][:, None]).contiguous()
-        wf_all = self._gather_t(wf)
-
-        v_all = stokeslet_device(d["r_fib_all"], wf_all, d["r_all"], eta)
-        # self subtraction uses the OWN fibers' wf only (f_c_fd.cpp:203-210)
-        corr = torch.bmm(d["G"], wf.reshape(nf, 3 * n, 1)).reshape(nf_nodes, 3)
-        v_all[:nf_nodes] -= corr
-
-        dens_all = None
-        if self.shell:
-            dens_all = self._gather_t(x_shell_local.reshape(-1, 3).contiguous())
-            f_dl = 2.0 * eta * torch.einsum("ni,nj->nij", d["sh_normals"],
-                                            dens_all).reshape(-1, 9).contiguous()
-            v_all[:nf_nodes] += stresslet_device(d["sh_nodes"], f_dl,
-                                                 d["r_fib"], eta)
-
-        res = torch.empty_like(x)
-        res[: 4 * nf_nodes] = self._fiber_block_device(
-            x_fib, v_all[:nf_nodes]).reshape(-1)
-        if self.shell:
-            # row-block GEMV against the GLOBAL density (periphery.cpp:34-47)
-            res[4 * nf_nodes:] = d["sh_A"] @ dens_all.reshape(-1) \
-                + v_all[nf_nodes:].reshape(-1)
-        return res
-
-    def _apply_precond_device(self, x):
-        d = self._dev
-        nf, n = d["nf"], d["n"]
-        res = torch.empty_like(x)
-        res[: 4 * nf * n] = d["lu"].solve(
-            x[: 4 * nf * n].reshape(nf, 4 * n)).reshape(-1)
-        if self.shell:
-            x_sh_all = self._gather_t(
-                x[4 * nf * n:].reshape(-1, 3).contiguous()).reshape(-1)
-            res[4 * nf * n:] = d["sh_Minv"] @ x_sh_all
-        return res
-
-    def solve(self, tol=1e-10, maxiter=200, restart=None, device_mode=None):
-        """Distributed GMRES over the rank-local slices. device_mode=True
-        runs the whole iteration on device tensors (matvec/precond above,
-        distributed dot-blocks in gmres); default auto-detects the product
-        backend. Requires >= 1 fiber per rank with uniform discretization."""
-        import torch.distributed as dist
-        from .gmres import gmres
-        from .system_fd import HipBackend
-
-        rhs = self.prep_state_for_solver()
-        if restart is None:
-            restart = min(200, maxiter)
-        distributed = dist.is_available() and dist.is_initialized() \
-            and dist.get_world_size() > 1
-        if device_mode is None:
-            device_mode = bool(self.fibers) and self._uniform \
-                and not self.bodies and isinstance(self.backend, HipBackend)
-        if device_mode and self.bodies:
-            raise NotImplementedError(
-                "bodies run on the host matvec path (round 2)")
-
-        if device_mode:
-            self._build_device_operators()
-            b = self.backend._t(rhs)
-            x, info = gmres(self._apply_matvec_device, b,
-                            precond=self._apply_precond_device,
-                            tol=tol, maxiter=maxiter, restart=restart,
-                            distributed=distributed)
-            if b.is_cuda:
-                self.backend.torch.cuda.synchronize()
-            self.solution = x.cpu().numpy()
-            return info
-
-        b = torch.from_numpy(rhs)
-        mv = lambda v: torch.from_numpy(self.apply_matvec(v.numpy()))
-        pc = lambda v: torch.from_numpy(self.apply_preconditioner(v.numpy()))
-        x, info = gmres(mv, b, precond=pc, tol=tol, maxiter=maxiter,
-                        restart=restart, distributed=distributed)
-        self.solution = x.numpy()
-        return info
-
-    def step(self, tol=1e-10, maxiter=200, restart=None):
-        """Solve then adopt: fibers locally, bodies on EVERY rank from the
-        broadcast rank-0 solution block (bc step Bcast,
-        body_container.cpp:49-60) so the replicated geometry stays
-        consistent."""
-        info = self.solve(tol=tol, maxiter=maxiter, restart=restart)
-        for f, a, b in self._fiber_slices():
-            f.step(self.solution[a:b])
-        if self.bodies:
-            full = self._bcast_body_solution(self.solution)
-            off = 0
-            for b in self.bodies:
-                b.step(self.dt, full[off: off + b.solution_size])
-                off += b.solution_size
-            # repin local attached fibers to the moved nucleation sites
-            # (f_c_fd.cpp:308-316 via system.cpp:488; bodies are replicated
-            # on every rank so each rank repins its own fiber block)
-            for f in self.fibers:
-                ib, js = getattr(f, "binding_site", (-1, -1))
-                if ib >= 0:
-                    delta = self.bodies[ib].nucleation_sites[js] - f.x[:, 0]
-                    f.x += delta[:, None]
-        return info
+            if requested:
+                raise NotImplementedError(
+                    "bodies run on the host matvec path (round 2)")
+            return False
+        return super()._device_mode(requested)
 
 
 def distribute_fibers(fibers, world, rank):

@@ -14,9 +14,20 @@ Pair interactions, batched LU and the shell GEMVs run through a pluggable
 backend: HipBackend (the product path — device kernels, fails loudly with
 no GPU) or any object with the same methods (tests inject the CPU oracle to
 validate the orchestration end-to-end off-GPU).
+
+The pipeline is written once, for a rank-local view of the system: the
+solution vector is [own fibers | own shell rows | body block], targets are
+the local nodes, and every place the reference communicates goes through
+self.comm (sharded.Comm) — fiber sources and the shell density are gathered,
+the body block is taken from rank 0, link forces are summed over ranks.
+SystemFD holds the single-rank communicator, for which all of these are the
+identity; system_dist.DistributedSystemFD is this class with a live
+communicator and the rank-local layout accessors.
 """
 
 import numpy as np
+
+from .sharded import Comm
 
 
 class HipBackend:
@@ -112,6 +123,9 @@ class Shell:
 
 
 class SystemFD:
+    # single rank: every collective in the pipeline below is the identity
+    comm = Comm(single=True)
+
     def __init__(self, fibers, eta, dt, shell=None, background_flow=None, backend=None,
                  periphery_interaction=None, bodies=None, periphery_shape=None,
                  periphery_binding=None, dynamic_instability=None, seed=130319):
@@ -159,13 +173,29 @@ class SystemFD:
     def fiber_sol_size(self):
         return sum(4 * f.n_nodes for f in self.fibers)
 
+    # The solution vector and the node array are RANK-LOCAL: [own fibers |
+    # own shell rows | body block]. The accessors below are the whole
+    # layout; a multi-rank subclass overrides them and nothing else.
+    def _own_shell_nodes(self):
+        """The shell nodes whose rows this rank solves for."""
+        return self.shell.nodes
+
     @property
     def shell_sol_size(self):
-        return 3 * self.shell.n_nodes if self.shell else 0
+        return 3 * len(self._own_shell_nodes()) if self.shell else 0
+
+    def _own_bodies(self):
+        """The bodies whose solution block lives in this rank's vector.
+        (self.bodies, the geometry, is the full set on every rank.)"""
+        return self.bodies
+
+    @property
+    def global_body_sol_size(self):
+        return sum(b.solution_size for b in self.bodies)
 
     @property
     def body_sol_size(self):
-        return sum(b.solution_size for b in self.bodies)
+        return sum(b.solution_size for b in self._own_bodies())
 
     @property
     def body_node_count(self):
@@ -184,26 +214,26 @@ class SystemFD:
             if self.bodies else np.zeros((0, 3))
 
     def all_nodes(self):
-        """Node order [fibers | shell | bodies] (system.cpp:408-418)."""
+        """The local targets, in node order [fibers | shell | bodies]
+        (system.cpp:408-418)."""
         parts = [self.fiber_nodes()]
         if self.shell:
-            parts.append(self.shell.nodes)
-        if self.bodies:
+            parts.append(self._own_shell_nodes())
+        if self._own_bodies():
             parts.append(self.body_nodes())
         return np.concatenate(parts, axis=0)
 
     def _body_sol_slices(self):
         out, off = [], self.fiber_sol_size + self.shell_sol_size
-        for b in self.bodies:
+        for b in self._own_bodies():
             out.append((b, off, off + b.solution_size))
             off += b.solution_size
         return out
 
     def _body_node_slices(self):
         """Slices into the [fibers | shell | bodies] node array."""
-        out, off = [], self.fiber_node_count + \
-            (self.shell.n_nodes if self.shell else 0)
-        for b in self.bodies:
+        out, off = [], self.fiber_node_count + self.shell_sol_size // 3
+        for b in self._own_bodies():
             out.append((b, off, off + b.n_nodes))
             off += b.n_nodes
         return out
@@ -232,6 +262,13 @@ class SystemFD:
                                  self.eta)
         return v
 
+    def _global_body_solution(self, x):
+        """The body block of the solution-layout vector x, from the rank
+        that holds it (rank 0) on every rank (system.cpp:309)."""
+        return self.comm.from_root(
+            x[self.fiber_sol_size + self.shell_sol_size:],
+            self.global_body_sol_size)
+
     def _fiber_slices(self):
         out, off = [], 0
         for f in self.fibers:
@@ -247,25 +284,41 @@ class SystemFD:
         return out
 
     # ---- fiber container operations ------------------------------------
+    def _build_self_stokeslets(self):
+        """Materialize the per-fiber self-stokeslets that prep reset (lazy:
+        the device-resident path never needs the host copies)."""
+        if not self.fibers or self.fibers[0].stokeslet is not None:
+            return
+        if self._uniform:
+            pts = np.stack([f.x.T for f in self.fibers])
+            G = self.backend.self_stokeslet_batch(pts, self.eta)
+            for f, g in zip(self.fibers, G):
+                f.stokeslet = g
+        else:
+            # mixed discretizations: per-fiber batches of one
+            for f in self.fibers:
+                f.stokeslet = self.backend.self_stokeslet_batch(
+                    f.x.T[None], self.eta)[0]
+
     def _fiber_flow(self, r_trg, fib_forces):
         """FiberContainerFiniteDifference::flow (f_c_fd.cpp:172-214):
         quadrature-weighted stokeslet of fiber forces at r_trg, minus the
-        per-fiber self term on the fiber's own slice of the targets."""
-        if not self.fibers:
+        per-fiber self term on the fiber's own slice of the targets. The
+        sources are ALL ranks' fibers (positions and weighted forces
+        gathered — the reference's per-apply MPI_Allgatherv); the self
+        term is this rank's fibers against their own wf, and their nodes
+        lead r_trg."""
+        if self.fibers:
+            w = np.concatenate([f.quadrature_weights() for f in self.fibers])
+            wf = fib_forces * w[:, None]
+        else:
+            wf = np.zeros((0, 3))
+        r_src = self.comm.gather_rows(self.fiber_nodes())
+        if not len(r_src):
             return np.zeros_like(r_trg)
-        if self.fibers[0].stokeslet is None:
-            if self._uniform:
-                pts = np.stack([f.x.T for f in self.fibers])
-                G = self.backend.self_stokeslet_batch(pts, self.eta)
-                for f, g in zip(self.fibers, G):
-                    f.stokeslet = g
-            else:
-                for f in self.fibers:
-                    f.stokeslet = self.backend.self_stokeslet_batch(
-                        f.x.T[None], self.eta)[0]
-        w = np.concatenate([f.quadrature_weights() for f in self.fibers])
-        wf = fib_forces * w[:, None]
-        vel = self.backend.stokeslet(self.fiber_nodes(), wf, r_trg, self.eta)
+        vel = self.backend.stokeslet(r_src, self.comm.gather_rows(wf), r_trg,
+                                     self.eta)
+        self._build_self_stokeslets()
         for f, a, b in self._fiber_node_slices():
             # stokeslet_ and wf are point-major interleaved (xyz per node),
             # matching the reference's VectorMap flattening (f_c_fd.cpp:204-208)
@@ -362,12 +415,10 @@ class SystemFD:
                                                b.external_torque])
                                for b in self.bodies])
             if np.any(ext_ft):
-                # global-sized zero densities (body_sol_size is rank-local
-                # in the distributed subclass; the flow's sources are the
-                # replicated global bodies)
+                # global-sized zero densities: the flow's sources are all
+                # the bodies, whichever rank holds their solution block
                 v_all += self._body_flow(
-                    r_all, np.zeros(sum(b.solution_size
-                                        for b in self.bodies)), ext_ft)
+                    r_all, np.zeros(self.global_body_sol_size), ext_ft)
 
         motor = motor + ext  # total_force_fibers (system.cpp:450)
         v_fib = v_all[:nf_nodes]
@@ -406,18 +457,14 @@ class SystemFD:
                                        if self.periphery_interaction is not None
                                        else None)
 
-        # preconditioner: batched LU of the (BC-applied) fiber operators
-        # (lazy — the device-resident solve path factors its own resident
-        # copy in _build_device_operators)
-        if self.fibers and self._uniform:
-            self._fiber_lu_solve = None
-        elif self.fibers:
-            solves = [self.backend.batched_lu(f.A[None]) for f in self.fibers]
-            self._fiber_lu_solve = None
-            self._fiber_lu_solves = solves
+        # preconditioner: batched LU of the (BC-applied) fiber operators,
+        # factored on first apply_preconditioner use (lazy — the
+        # device-resident solve path factors its own resident copy in
+        # _build_device_operators)
+        self._fiber_lu_solves = None
 
         rhs_parts = [f.RHS for f in self.fibers]
-        sh_nodes = self.shell.n_nodes if self.shell else 0
+        sh_nodes = self.shell_sol_size // 3
         if self.shell:
             v_shell = v_all[nf_nodes: nf_nodes + sh_nodes]
             rhs_parts.append(-v_shell.reshape(-1))  # update_RHS, periphery.cpp:86
@@ -427,21 +474,22 @@ class SystemFD:
         return self.RHS
 
     def apply_matvec(self, x):
-        """system.cpp:269-324 (fibers + shell + bodies)."""
+        """system.cpp:269-324 (fibers + shell + bodies): all ranks' sources,
+        this rank's targets and rows."""
         nf_nodes = self.fiber_node_count
-        sh_nodes = self.shell.n_nodes if self.shell else 0
+        sh_nodes = self.shell_sol_size // 3
         x_fib = x[: self.fiber_sol_size]
         x_shell = x[self.fiber_sol_size: self.fiber_sol_size + self.shell_sol_size]
-        x_bodies = x[self.fiber_sol_size + self.shell_sol_size:]
         r_all = self.all_nodes()
 
         fw = self._apply_fiber_force(x_fib)
         v_all = self._fiber_flow(r_all, fw)
 
         if self.shell:
-            # shell double layer flows to fibers AND bodies, not to itself
-            # (system.cpp:302-305,314-316)
-            dens = x_shell.reshape(-1, 3)
+            # the GLOBAL density (periphery.cpp:26,44 Allgatherv); its
+            # double layer flows to fibers AND bodies, not to the shell
+            # itself (system.cpp:302-305,314-316)
+            dens = self.comm.gather_rows(x_shell.reshape(-1, 3))
             trg = np.concatenate([r_all[:nf_nodes],
                                   r_all[nf_nodes + sh_nodes:]])
             if len(trg):
@@ -452,13 +500,24 @@ class SystemFD:
 
         vel_on_fiber = None
         if self.bodies:
-            # fiber<->body link conditions + body flow (system.cpp:308-317)
+            # fiber<->body link conditions + body flow (system.cpp:308-317).
+            # Bodies follow the reference's ownership model: the geometry
+            # is replicated on every rank, the solution block lives in
+            # rank 0's vector and is broadcast per apply
+            # (body_container.hpp:99, system.cpp:309), and the link forces
+            # each rank computes from its own fibers are summed
+            # (body_container.cpp:131)
             from .body import calculate_link_conditions
-            body_vels = np.stack([
-                x[a + 3 * b.n_nodes: bb] for b, a, bb in self._body_sol_slices()])
+            x_bodies = self._global_body_solution(x)
+            body_vels, off = [], 0
+            for b in self.bodies:
+                body_vels.append(x_bodies[off + 3 * b.n_nodes:
+                                          off + b.solution_size])
+                off += b.solution_size
             vel_on_fiber, body_ft = calculate_link_conditions(
-                self.fibers, x_fib, body_vels, self.bodies)
-            v_all += self._body_flow(r_all, x_bodies, body_ft)
+                self.fibers, x_fib, np.stack(body_vels), self.bodies)
+            v_all += self._body_flow(r_all, x_bodies,
+                                     self.comm.sum(body_ft))
 
         res = np.zeros_like(x)
         v_fib = v_all[:nf_nodes]
@@ -467,9 +526,11 @@ class SystemFD:
             vb = vel_on_fiber[i] if vel_on_fiber is not None else None
             res[a:b] = f.matvec(x_fib[a:b], v_fib[na:nb].T, vb)
         if self.shell:
+            # own rows of the dense operator against the global density
+            # (row-distributed dense ops, periphery.cpp:34-47)
             v_shell = v_all[nf_nodes: nf_nodes + sh_nodes]
             res[self.fiber_sol_size: self.fiber_sol_size + self.shell_sol_size] = \
-                self._shell_matvec(x_shell) + v_shell.reshape(-1)
+                self._shell_matvec(dens.reshape(-1)) + v_shell.reshape(-1)
         for (b, a, bb), (_, na, nb) in zip(self._body_sol_slices(),
                                            self._body_node_slices()):
             res[a:bb] = b.matvec(v_all[na:nb], x[a:bb])
@@ -478,23 +539,26 @@ class SystemFD:
     def apply_preconditioner(self, x):
         """system.cpp:248-263."""
         res = np.zeros_like(x)
-        x_fib = x[: self.fiber_sol_size]
-        if self.fibers:
-            if self._uniform:
-                if self._fiber_lu_solve is None:
-                    A_batch = np.stack([f.A for f in self.fibers])
-                    self._fiber_lu_solve = self.backend.batched_lu(A_batch)
-                m = 4 * self.fibers[0].n_nodes
-                sol = self._fiber_lu_solve(x_fib.reshape(len(self.fibers), m))
-                res[: self.fiber_sol_size] = sol.reshape(-1)
-            else:
-                for (f, a, b), solve in zip(self._fiber_slices(),
-                                            self._fiber_lu_solves):
-                    res[a:b] = solve(x_fib[a:b][None])[0]
+        # one batched LU over all fibers when they share a discretization,
+        # otherwise per-fiber batches of one
+        batches = [self.fibers] if self._uniform and self.fibers \
+            else [[f] for f in self.fibers]
+        if self._fiber_lu_solves is None:
+            self._fiber_lu_solves = [
+                self.backend.batched_lu(np.stack([f.A for f in fibs]))
+                for fibs in batches]
+        off = 0
+        for fibs, solve in zip(batches, self._fiber_lu_solves):
+            m = 4 * fibs[0].n_nodes
+            end = off + len(fibs) * m
+            res[off:end] = solve(x[off:end].reshape(len(fibs), m)).reshape(-1)
+            off = end
         if self.shell:
+            # own rows of M_inv against the global shell vector
             sh = slice(self.fiber_sol_size,
                        self.fiber_sol_size + self.shell_sol_size)
-            res[sh] = self._shell_precond(x[sh])
+            res[sh] = self._shell_precond(
+                self.comm.gather_rows(x[sh].reshape(-1, 3)).reshape(-1))
         for b, a, bb in self._body_sol_slices():
             res[a:bb] = b.apply_preconditioner(x[a:bb])
         return res
@@ -527,6 +591,8 @@ class SystemFD:
         d["P_ds"] = T(f0.mats["P_downsample_bc"])                    # (4n-14, 4n)
         d["D1preT"] = T((f0.mats["D_1_0"] * (2.0 / f0.length_prev)).T)
         d["r_fib"] = T(self.fiber_nodes())
+        # the one solve-static gather: fiber source positions of all ranks
+        d["r_fib_all"] = self.comm.gather_rows(d["r_fib"])
         d["r_all"] = T(self.all_nodes())
         d["plus_vel"] = T(np.array(
             [1.0 if f.bc_plus[0] == "Velocity" else 0.0 for f in self.fibers]))
@@ -541,7 +607,8 @@ class SystemFD:
             # ~1.5x the axpy path on these square operators (measured
             # 0.96 vs 1.43 ms at 24576^2, tools/prof_iter.py), so store
             # X^T contiguous and apply as mv(X_T.t(), v). HBM cost is one
-            # extra copy of each operator — trivial in 288 GB.
+            # extra copy of each operator — trivial in 288 GB. A rank's
+            # (3n_local, 3N) row block takes the same form.
             if getattr(self.shell, "_A_T", None) is None:
                 self.shell._A_T = d["sh_A"].t().contiguous()
                 self.shell._Minv_T = d["sh_Minv"].t().contiguous()
@@ -589,13 +656,16 @@ class SystemFD:
     def _apply_matvec_device(self, x):
         """apply_matvec entirely on device (torch fp64 CUDA vector in/out);
         covers fibers + shell + bodies (node order [fib | shell | body],
-        system.cpp:269-324)."""
+        system.cpp:269-324). The collectives are apply_matvec's: wf and
+        the shell density are gathered once per apply (RCCL over xGMI on
+        GPUs), the fiber positions once per build; bodies here are
+        single-rank only."""
         import torch
         from .evaluator import stokeslet_device, stresslet_device
         d = self._dev
         nf, n = d["nf"], d["n"]
         eta = self.eta
-        nf_nodes = nf * n
+        nf_nodes = nf * n  # LOCAL fiber nodes (targets); sources are global
         sh_size = self.shell_sol_size
         sh_nodes_n = sh_size // 3
         x_fib = x[: 4 * nf_nodes].reshape(nf, 4 * n)
@@ -607,15 +677,18 @@ class SystemFD:
         fw_nodes = fw.reshape(nf, 3, n).permute(0, 2, 1).reshape(nf_nodes, 3)
         wf = (fw_nodes * d["w"][:, None]).contiguous()
 
-        v_all = stokeslet_device(d["r_fib"], wf, d["r_all"], eta)
-        # per-fiber self subtraction (point-major, f_c_fd.cpp:203-210)
+        v_all = stokeslet_device(d["r_fib_all"], self.comm.gather_rows(wf),
+                                 d["r_all"], eta)
+        # per-fiber self subtraction, on the OWN fibers' wf only
+        # (point-major, f_c_fd.cpp:203-210)
         wf_pm = wf.reshape(nf, 3 * n, 1)
         corr = torch.bmm(d["G"], wf_pm).reshape(nf_nodes, 3)
         v_all[:nf_nodes] -= corr
 
         if self.shell:
-            # shell double layer flows to fibers and bodies, not to itself
-            dens = x_shell.reshape(-1, 3)
+            # shell double layer (of the global density) flows to fibers
+            # and bodies, not to itself
+            dens = self.comm.gather_rows(x_shell.reshape(-1, 3))
             f_dl = 2.0 * eta * torch.einsum("ni,nj->nij", d["sh_normals"],
                                             dens).reshape(-1, 9).contiguous()
             v_all[:nf_nodes] += stresslet_device(d["sh_nodes"], f_dl,
@@ -681,9 +754,10 @@ class SystemFD:
         res[: 4 * nf_nodes] = self._fiber_block_device(
             x_fib, v_all[:nf_nodes], vel7).reshape(-1)
         if self.shell:
+            # own rows against the global density (periphery.cpp:34-47)
             v_shell = v_all[nf_nodes: nf_nodes + sh_nodes_n].reshape(-1)
             res[4 * nf_nodes: 4 * nf_nodes + sh_size] = \
-                torch.addmv(v_shell, d["sh_A_T"].t(), x_shell)
+                torch.addmv(v_shell, d["sh_A_T"].t(), dens.reshape(-1))
         if self.bodies:
             off = 0
             off_node = nf_nodes + sh_nodes_n
@@ -738,8 +812,10 @@ class SystemFD:
         res = torch.empty_like(x)
         res[: 4 * nf * n] = d["lu"].solve(x[: 4 * nf * n].reshape(nf, 4 * n)).reshape(-1)
         if self.shell:
+            x_sh = x[4 * nf * n: 4 * nf * n + sh_size]
             res[4 * nf * n: 4 * nf * n + sh_size] = torch.mv(
-                d["sh_Minv_T"].t(), x[4 * nf * n: 4 * nf * n + sh_size])
+                d["sh_Minv_T"].t(),
+                self.comm.gather_rows(x_sh.reshape(-1, 3)).reshape(-1))
         if self.bodies:
             off = 4 * nf * n + sh_size
             for bd in d["bodies"]:
@@ -748,6 +824,14 @@ class SystemFD:
                     x[off: off + m].unsqueeze(0)).squeeze(0)
                 off += m
         return res
+
+    def _device_mode(self, requested):
+        """solve(device_mode=): None picks the device-resident iteration
+        whenever it applies (uniform fibers on the HIP backend)."""
+        if requested is None:
+            return (bool(self.fibers) and self._uniform
+                    and isinstance(self.backend, HipBackend))
+        return requested
 
     def solve(self, tol=1e-10, maxiter=200, restart=None, device_mode=None,
               warm_start=None):
@@ -780,16 +864,17 @@ class SystemFD:
         x0_np = prev if (warm_start and prev is not None
                          and prev.shape == rhs.shape) else None
 
-        if device_mode is None:
-            device_mode = (bool(self.fibers) and self._uniform
-                           and isinstance(self.backend, HipBackend))
-        if device_mode:
+        # rank-local slices of a block-row-distributed vector: the GMRES
+        # dots and norms reduce over ranks (the Tpetra/Belos dots)
+        distributed = self.comm.world > 1
+        if self._device_mode(device_mode):
             self._build_device_operators()
             b = self.backend._t(rhs)
             x0 = self.backend._t(x0_np) if x0_np is not None else None
             x, info = gmres(self._apply_matvec_device, b,
                             precond=self._apply_precond_device,
-                            tol=tol, maxiter=maxiter, restart=restart, x0=x0)
+                            tol=tol, maxiter=maxiter, restart=restart, x0=x0,
+                            distributed=distributed)
             if b.is_cuda:
                 self.backend.torch.cuda.synchronize()
             self.solution = x.cpu().numpy()
@@ -800,7 +885,7 @@ class SystemFD:
         mv = lambda v: torch.from_numpy(self.apply_matvec(v.numpy()))
         pc = lambda v: torch.from_numpy(self.apply_preconditioner(v.numpy()))
         x, info = gmres(mv, b, precond=pc, tol=tol, maxiter=maxiter,
-                        restart=restart, x0=x0)
+                        restart=restart, x0=x0, distributed=distributed)
         self.solution = x.numpy()
         return info
 
@@ -808,12 +893,19 @@ class SystemFD:
         """system.cpp:482-493: solve then adopt positions, then repin
         body-attached fibers to their (moved) nucleation sites
         (FiberContainerFiniteDifference::repin_to_bodies,
-        fiber_container_finite_difference.cpp:308-316 via system.cpp:488)."""
+        fiber_container_finite_difference.cpp:308-316 via system.cpp:488).
+        Fibers adopt locally; bodies adopt on EVERY rank from rank 0's
+        solution block (bc step Bcast, body_container.cpp:49-60) so the
+        replicated geometry stays consistent, and each rank repins its own
+        fibers."""
         info = self.solve(tol=tol, maxiter=maxiter, restart=restart)
         for f, a, b in self._fiber_slices():
             f.step(self.solution[a:b])
-        for b, a, bb in self._body_sol_slices():
-            b.step(self.dt, self.solution[a:bb])
+        if self.bodies:
+            x_bodies, off = self._global_body_solution(self.solution), 0
+            for b in self.bodies:
+                b.step(self.dt, x_bodies[off: off + b.solution_size])
+                off += b.solution_size
         self.repin_to_bodies()
         return info
 
@@ -831,9 +923,7 @@ class SystemFD:
         gap = center distance - 2*fiber_radius (clamped >= 0), cutoff
         d_max (default 5*l_0 + 2*fiber_radius)."""
         from scipy.spatial import cKDTree
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() \
-                and dist.get_world_size() > 1:
+        if self.comm.world > 1:
             raise NotImplementedError(
                 "fiber-fiber steric repulsion needs a global neighbor "
                 "search; not wired into the distributed prep yet")

@@ -70,8 +70,8 @@ def _dist_worker(rank, world, init_file, q, device_mode=False):
 @pytest.mark.parametrize("device_mode", [False, True],
                          ids=["host", "device-layout"])
 def test_distributed_solve_matches_single_process(device_mode):
-    """device-layout runs the device-resident distributed iteration
-    (system_dist._apply_matvec_device) on CPU tensors with oracle-backed
+    """device-layout runs the device-resident iteration under a world-2
+    communicator (SystemFD._apply_matvec_device) on CPU tensors with oracle-backed
     kernel fakes — the orchestration (gathers, batched blocks, row-block
     GEMVs, distributed GMRES on tensors) is what's under test; the HIP
     kernels themselves are covered by the gpu-marked suites."""
@@ -203,6 +203,23 @@ def test_distributed_body_solve_matches_single_process():
         assert np.allclose(pos, body.position, atol=1e-10)
         assert np.allclose(vel, body.velocity, atol=1e-10)
         assert np.allclose(quat, body.orientation, atol=1e-12)
+
+
+def test_distributed_bodies_stay_on_host_path():
+    """Bodies in the device-resident iteration are single-rank only: the
+    distributed system refuses a forced device mode when it has bodies and
+    never auto-selects it. (No process group: every collective is the
+    identity.)"""
+    from skellysim_amd.system_dist import DistributedSystemFD
+    from oracle_backend import OracleBackend
+    body, fibers = _body_problem()
+    sys_ = DistributedSystemFD(fibers, eta=1.0, dt=0.05,
+                               backend=OracleBackend(), bodies=[body])
+    with pytest.raises(NotImplementedError):
+        sys_.solve(device_mode=True)
+    info = sys_.solve()
+    assert info["converged"], info
+    assert not hasattr(sys_, "_dev")  # host path: no device operators built
 
 
 def _dist_triple_worker(rank, world, init_file, q):
