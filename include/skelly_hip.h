@@ -51,6 +51,14 @@ extern "C" {
  * warmup. */
 void skelly_set_persistent_ws(int on);
 
+/* Mode of the pair kernels' unmasked fast path, overriding the
+ * SKELLY_PAIR_FASTPATH env var: 0 = off (every pair goes through the r==0
+ * mask), 1 = auto (default: on for launches whose blocks each walk >= 8192
+ * sources, where its rerun of chunks that hold coincident points cannot
+ * outweigh its gain), 2 = always on. Results are bit-identical in every
+ * mode; the switch exists for A/B timing and for the tests that check that. */
+void skelly_set_pair_fastpath(int mode);
+
 /* Human-readable build id ("skelly-hip <ver> gfx950"). */
 const char *skelly_hip_version(void);
 

@@ -53,6 +53,8 @@ def _bind(lib):
     lib.skelly_fp64_peak_tflops.argtypes = [ctypes.POINTER(ctypes.c_double)]
     lib.skelly_set_persistent_ws.argtypes = [ctypes.c_int]
     lib.skelly_set_persistent_ws.restype = None
+    lib.skelly_set_pair_fastpath.argtypes = [ctypes.c_int]
+    lib.skelly_set_pair_fastpath.restype = None
 
 
 def lib():
@@ -71,6 +73,14 @@ def lib():
             raise RuntimeError(f"failed to load {_LIB_PATH}: {e}") from e
         _bind(_lib)
     return _lib
+
+
+def set_pair_fastpath(mode):
+    """Mode of the pair kernels' unmasked fast path: 0 off (every pair goes
+    through the r == 0 mask), 1 auto (default: on for launches whose blocks
+    each walk >= 8192 sources), 2 always on. Results are bit-identical in
+    every mode."""
+    lib().skelly_set_pair_fastpath(int(mode))
 
 
 def check(rc, what):

@@ -12,13 +12,30 @@
  * which used 32-thread blocks and accumulated into global memory every tile):
  *   - 256-thread blocks (4 wave64s), TPT targets per thread held in VGPRs;
  *     velocity accumulates in registers and is written once.
- *   - Sources staged through LDS in TILE=512-point tiles (24 KB stokeslet,
- *     48 KB stresslet). Inner-loop LDS reads are wave-uniform -> broadcast,
- *     conflict-free by construction.
- *   - fp64 rsqrt: raw v_rsq_f64 + one 4-op Newton step (see rsq_refined),
- *     skipping libm's fp-class edge handling because r^2 is a finite sum of
- *     squares and the r^2==0 case is masked explicitly (reference masks it
- *     too, kernels.cu:39,70).
+ *   - Sources staged through LDS in TILE=512-point tiles (36 KB stokeslet
+ *     and oseen incl. the f/4 copy below, 48 KB stresslet). Inner-loop LDS
+ *     reads are wave-uniform -> broadcast, conflict-free by construction.
+ *   - fp64 rsqrt: raw v_rsq_f64 + one 3-op Newton step that returns
+ *     R = 2/sqrt(x) (see rsq_x2). The factor 2 (and its powers R^3 = 8/r^3,
+ *     R^5 = 32/r^5) never costs a pair-loop instruction: where it is global
+ *     the host divides Params::scale by K::ACC_FOLD; stokeslet and oseen,
+ *     which mix R and R^3, read a second LDS copy f/4 of the strength for
+ *     the dot product so that every accumulator is exactly 2x the plain
+ *     sum. All rescalings are powers of two -> results are bit-identical
+ *     to the 4-op form (for values that stay normal fp64).
+ *   - The r^2==0 mask (reference: kernels.cu:39,70) is off the fast path.
+ *     Each tile is walked in CHUNK-source pieces: a wave saves its
+ *     accumulators, runs the chunk unmasked (a coincident pair gives
+ *     rsq(0) = inf, 0*inf = NaN, so the accumulator goes NaN), tests the
+ *     accumulators, and only if some lane saw a NaN (wave-uniform branch)
+ *     restores them and reruns the chunk masked - same arithmetic, same
+ *     source order, so the result does not depend on which path ran. A
+ *     NaN that comes from the inputs takes the rerun once per chunk and
+ *     stays NaN. Regularized oseen turns r = 0 into a finite 1/reg, so it
+ *     tracks min(high dword of r^2) per chunk instead (one b32 op a pair).
+ *     skelly_set_pair_fastpath(0) runs the masked path everywhere; by
+ *     default small launches (under 128 chunks a block) stay masked too,
+ *     see pair_fastpath_mode.
  *   - Accumulation order per target is source order (tile-major), fixed ->
  *     bit-reproducible for a given shard layout and slice count.
  *   - Small target counts (< 512 workgroups at one target/thread) switch to
@@ -40,52 +57,83 @@
 #define BLOCK 256
 #define TILE 512
 
-/* v_rsq_f64 + one refinement step. Inputs here are finite and >= 0;
- * x == 0 must be masked by the caller. */
-__device__ inline double rsq_refined(double x) {
+/* Sources per unmasked chunk between two accumulator checks (multiple of
+ * SKELLY_UNROLL, divides TILE). Measured on MI355X, profiles/pair_fastpath.md. */
+#ifndef SKELLY_CHUNK
+#define SKELLY_CHUNK 64
+#endif
+
+/* R = 2/sqrt(x): v_rsq_f64 + one refinement step with the constant factor
+ * left out. Inputs here are finite and >= 0; x == 0 gives NaN (inf seed,
+ * 0*inf), which the caller masks or detects. */
+__device__ inline double rsq_x2(double x) {
     double y;
     asm("v_rsq_f64 %0, %1" : "=v"(y) : "v"(x));
 #ifdef SKELLY_RSQ_PRECISE
     /* 5-op Householder (2nd order) step — the same polish ROCm libm applies:
-     * cubic convergence, <= 2 ulp of fp64. */
+     * cubic convergence, <= 2 ulp of fp64 — plus the doubling, so that the
+     * folded scales below hold for this variant too. */
     const double e = __builtin_fma(-x * y, y, 1.0);
     const double c = __builtin_fma(e, 0.375, 0.5);
-    return __builtin_fma(y * e, c, y);
+    return 2.0 * __builtin_fma(y * e, c, y);
 #else
-    /* Default: 4-op quadratic Newton step, y' = -(0.5*y) * ((x*y)*y - 3).
-     * Measured on MI355X (profiles/rocprof_r01.md): identical norm-relative
-     * parity vs the CPU oracle (~5e-16 at 2e4x4096 incl. near-coincident
-     * pairs) and +4.6%/+2.9%/+2.2% on stokeslet/stresslet/oseen over the
-     * Householder form — v_rsq_f64's seed is accurate enough that one
-     * quadratic step reaches the fp64 rounding floor of the summation. */
+    /* Default: quadratic Newton step y' = (0.5*y) * (3 - (x*y)*y), issued as
+     * the 3 ops t = x*y, q = fma(-t, y, 3), R = y*q = 2y' (exactly: the
+     * missing 0.5 is a power of two). Measured on MI355X
+     * (profiles/rocprof_r01.md): identical norm-relative parity vs the CPU
+     * oracle (~5e-16 at 2e4x4096 incl. near-coincident pairs) and
+     * +4.6%/+2.9%/+2.2% on stokeslet/stresslet/oseen over the Householder
+     * form — v_rsq_f64's seed is accurate enough that one quadratic step
+     * reaches the fp64 rounding floor of the summation. */
     const double t = x * y;
-    const double w = __builtin_fma(t, y, -3.0);
-    return (-0.5 * y) * w;
+    const double q = __builtin_fma(-t, y, 3.0);
+    return y * q;
 #endif
 }
 
-/* ---- kernel functors ------------------------------------------------- */
+/* 1/sqrt(x) for the dense builders below (setup-time, not hot). */
+__device__ inline double rsq_refined(double x) { return 0.5 * rsq_x2(x); }
+
+/* ---- kernel functors -------------------------------------------------
+ * pair<MASKED>() adds one source's contribution to one target's
+ * accumulators. With R = 2/r the accumulators hold ACC_FOLD times the plain
+ * sum; the launch helpers divide Params::scale by ACC_FOLD.
+ *   HAS_MASK   the kernel zeroes coincident pairs; MASKED=false leaves the
+ *              select out and must make a coincident pair detectable.
+ *   NAN_PROBE  an unmasked coincident pair turns the accumulators NaN
+ *              (else pair<false> lowers `zmin` to 0 on one).
+ *   AUXDIM     doubles per source of the second LDS copy g = f/4 (0: none). */
 
 struct Stokeslet {
+    static constexpr int MIN_WAVES = 3;
     static constexpr int SRCDIM = 3;
+    static constexpr int AUXDIM = 3;
+    static constexpr bool HAS_MASK = true;
+    static constexpr bool NAN_PROBE = true;
+    static constexpr double ACC_FOLD = 2.0;
     struct Params {
-        double scale; /* 1/(8*pi) [ / eta when folded] */
+        double scale; /* 1/(8*pi) [ / eta when folded] / ACC_FOLD */
     };
-    /* u += (1/r)(f + rhat (f.rhat)); r = t - s; r==0 -> 0 (kernels.cu:62-76) */
+    /* u += (1/r)(f + rhat (f.rhat)); r = t - s; r==0 -> 0 (kernels.cu:62-76).
+     * With R = 2/r and g = f/4: (g.d) R^2 = (f.d)/r^2, so each term is
+     * R (f + d (f.d)/r^2) = 2x the plain one. */
+    template <bool MASKED>
     __device__ static inline void pair(const double t[3], const double sp[3], const double f[3],
-                                       double acc[3], const Params &) {
+                                       const double g[3], double acc[3], const Params &,
+                                       unsigned &) {
         const double dx = t[0] - sp[0];
         const double dy = t[1] - sp[1];
         const double dz = t[2] - sp[2];
         double r2 = dx * dx;
         r2 = __builtin_fma(dy, dy, r2);
         r2 = __builtin_fma(dz, dz, r2);
-        double rinv = rsq_refined(r2);
-        rinv = (r2 == 0.0) ? 0.0 : rinv; /* kernels.cu:70 */
+        double rinv = rsq_x2(r2);
+        if (MASKED)
+            rinv = (r2 == 0.0) ? 0.0 : rinv; /* kernels.cu:70 */
         const double rinv2 = rinv * rinv;
-        double fdotr = f[0] * dx;
-        fdotr = __builtin_fma(f[1], dy, fdotr);
-        fdotr = __builtin_fma(f[2], dz, fdotr);
+        double fdotr = g[0] * dx;
+        fdotr = __builtin_fma(g[1], dy, fdotr);
+        fdotr = __builtin_fma(g[2], dz, fdotr);
         const double inner = fdotr * rinv2;
         acc[0] = __builtin_fma(rinv, __builtin_fma(dx, inner, f[0]), acc[0]);
         acc[1] = __builtin_fma(rinv, __builtin_fma(dy, inner, f[1]), acc[1]);
@@ -95,23 +143,31 @@ struct Stokeslet {
 };
 
 struct Stresslet {
+    static constexpr int MIN_WAVES = 2;
     static constexpr int SRCDIM = 9;
+    static constexpr int AUXDIM = 0;
+    static constexpr bool HAS_MASK = true;
+    static constexpr bool NAN_PROBE = true;
+    static constexpr double ACC_FOLD = 32.0; /* R^5 = 32/r^5 */
     struct Params {
-        double scale; /* 1/(8*pi) [ / eta when folded] */
+        double scale; /* 1/(8*pi) [ / eta when folded] / ACC_FOLD */
     };
     /* u += -3 (d^T S d)/r^5 d; d = t - s; r==0 -> 0 (kernels.cu:29-54) */
+    template <bool MASKED>
     __device__ static inline void pair(const double t[3], const double sp[3], const double f[9],
-                                       double acc[3], const Params &) {
+                                       const double *, double acc[3], const Params &,
+                                       unsigned &) {
         const double dx = t[0] - sp[0];
         const double dy = t[1] - sp[1];
         const double dz = t[2] - sp[2];
         const double dxx = dx * dx, dyy = dy * dy, dzz = dz * dz;
         double dr2 = dxx + dyy;
         dr2 += dzz;
-        const double rinv = rsq_refined(dr2);
+        const double rinv = rsq_x2(dr2);
         const double rinv2 = rinv * rinv;
         double rinv5 = rinv * rinv2 * rinv2;
-        rinv5 = (dr2 == 0.0) ? 0.0 : rinv5; /* kernels.cu:39 */
+        if (MASKED)
+            rinv5 = (dr2 == 0.0) ? 0.0 : rinv5; /* kernels.cu:39 */
         /* coeff = sxx dx^2 + syy dy^2 + szz dz^2 + (sxy+syx) dx dy
          *       + (sxz+szx) dx dz + (syz+szy) dy dz   (kernels.cu:45-48) */
         double coeff = f[0] * dxx;
@@ -129,9 +185,14 @@ struct Stresslet {
 };
 
 struct OseenContract {
+    static constexpr int MIN_WAVES = 3;
     static constexpr int SRCDIM = 3;
+    static constexpr int AUXDIM = 3;
+    static constexpr bool HAS_MASK = true;
+    static constexpr bool NAN_PROBE = false; /* r = 0 regularizes to a finite 1/reg */
+    static constexpr double ACC_FOLD = 2.0;
     struct Params {
-        double scale; /* factor = 1/(8*pi*eta), hoisted out of the pair loop */
+        double scale; /* factor = 1/(8*pi*eta) / ACC_FOLD, hoisted out of the pair loop */
         double reg2;
         double eps2;
     };
@@ -139,9 +200,15 @@ struct OseenContract {
      * else fr=1/sqrt(dr^2+reg^2), gr that cubed. The dr > eps comparison is
      * evaluated as dr2 > eps^2 (monotone equivalent for exact values; can
      * differ only when sqrt rounding straddles eps itself). `factor` is
-     * applied once at the end (linear in the sum). */
+     * applied once at the end (linear in the sum). With y = 2*fr and
+     * g = rho/4: y^3 (d.g) = 2 gr (d.rho), so both terms are 2x.
+     * Unmasked, a coincident pair would add the finite fr*rho, so the high
+     * dword of dr2 is min-tracked instead: 0 there means dr2 < 2^-1022
+     * (zero or subnormal) and sends the chunk to the masked rerun. */
+    template <bool MASKED>
     __device__ static inline void pair(const double t[3], const double sp[3], const double rho[3],
-                                       double acc[3], const Params &p) {
+                                       const double g[3], double acc[3], const Params &p,
+                                       unsigned &zmin) {
         const double dx = sp[0] - t[0]; /* src - trg, kernels.cpp:99-101 */
         const double dy = sp[1] - t[1];
         const double dz = sp[2] - t[2];
@@ -149,12 +216,17 @@ struct OseenContract {
         dr2 = __builtin_fma(dy, dy, dr2);
         dr2 = __builtin_fma(dz, dz, dr2);
         const double denom2 = (dr2 > p.eps2) ? dr2 : dr2 + p.reg2;
-        double y = rsq_refined(denom2);
-        y = (dr2 == 0.0) ? 0.0 : y; /* kernels.cpp:105-106 skip */
+        double y = rsq_x2(denom2);
+        if (MASKED) {
+            y = (dr2 == 0.0) ? 0.0 : y; /* kernels.cpp:105-106 skip */
+        } else {
+            const unsigned hi = (unsigned)__double2hiint(dr2);
+            zmin = hi < zmin ? hi : zmin;
+        }
         const double y3 = y * (y * y);
-        double ddotrho = dx * rho[0];
-        ddotrho = __builtin_fma(dy, rho[1], ddotrho);
-        ddotrho = __builtin_fma(dz, rho[2], ddotrho);
+        double ddotrho = dx * g[0];
+        ddotrho = __builtin_fma(dy, g[1], ddotrho);
+        ddotrho = __builtin_fma(dz, g[2], ddotrho);
         const double c = y3 * ddotrho;
         acc[0] = __builtin_fma(y, rho[0], acc[0]);
         acc[1] = __builtin_fma(y, rho[1], acc[1]);
@@ -167,18 +239,25 @@ struct OseenContract {
 };
 
 struct Rotlet {
+    static constexpr int MIN_WAVES = 3;
     static constexpr int SRCDIM = 3;
+    static constexpr int AUXDIM = 0;
+    static constexpr bool HAS_MASK = false;
+    static constexpr bool NAN_PROBE = false;
+    static constexpr double ACC_FOLD = 8.0; /* y^3 = 8*fr */
     struct Params {
-        double scale; /* factor = 1/(8*pi*eta), applied at the end as the
-                         reference does (kernels.cpp:239) */
+        double scale; /* factor = 1/(8*pi*eta) / ACC_FOLD, applied at the end
+                         as the reference does (kernels.cpp:239) */
         double reg2;
         double eps2;
     };
     /* kernels.cpp:218-236: dr = dr2 < eps^2 ? sqrt(reg2+dr2) : sqrt(dr2)
      * (no dr==0 skip); fr = 1/dr^3; u += fr * (d x' rho) with the reference's
      * sign convention u_x += fr*(dz*rho_y - dy*rho_z), d = trg - src. */
+    template <bool MASKED>
     __device__ static inline void pair(const double t[3], const double sp[3], const double rho[3],
-                                       double acc[3], const Params &p) {
+                                       const double *, double acc[3], const Params &p,
+                                       unsigned &) {
         const double dx = t[0] - sp[0];
         const double dy = t[1] - sp[1];
         const double dz = t[2] - sp[2];
@@ -186,7 +265,7 @@ struct Rotlet {
         dr2 = __builtin_fma(dy, dy, dr2);
         dr2 = __builtin_fma(dz, dz, dr2);
         const double denom2 = (dr2 < p.eps2) ? dr2 + p.reg2 : dr2;
-        const double y = rsq_refined(denom2);
+        const double y = rsq_x2(denom2);
         const double fr = y * (y * y);
         const double cx = __builtin_fma(dz, rho[1], -(dy * rho[2]));
         const double cy = __builtin_fma(dx, rho[2], -(dz * rho[0]));
@@ -199,9 +278,17 @@ struct Rotlet {
 };
 
 struct StressletNormalDensity {
+    static constexpr int MIN_WAVES = 3;
     static constexpr int SRCDIM = 6; /* normal[3] + density[3] per source */
+    static constexpr int AUXDIM = 0;
+    static constexpr bool HAS_MASK = true;
+    /* Unmasked, d == 0 gives f0 = (+-0)*(+-0)*rinv5: the same signed zero as
+     * the masked rinv5 = +0 while the regularized rinv5 is finite, and NaN
+     * (0*inf, or the rsq(0) seed when reg == 0) otherwise. */
+    static constexpr bool NAN_PROBE = true;
+    static constexpr double ACC_FOLD = 32.0; /* y^5 = 32/r^5 */
     struct Params {
-        double scale; /* -3/(4*pi), kernels.cpp:311 (no eta dependence) */
+        double scale; /* -3/(4*pi) / ACC_FOLD, kernels.cpp:311 (no eta dependence) */
         double reg2;
         double eps2;
     };
@@ -209,8 +296,10 @@ struct StressletNormalDensity {
      * Sdn_i += (d.rho_j)(d.n_j)/r^5 d, d = trg - src; r_norm < eps ->
      * sqrt(r^2+reg^2) (kernels.cpp:320-323). The reference's i==j skip is a
      * d==0 mask here (identical: the numerator is ~d^3). */
+    template <bool MASKED>
     __device__ static inline void pair(const double t[3], const double sp[3], const double f[6],
-                                       double acc[3], const Params &p) {
+                                       const double *, double acc[3], const Params &p,
+                                       unsigned &) {
         const double dx = t[0] - sp[0];
         const double dy = t[1] - sp[1];
         const double dz = t[2] - sp[2];
@@ -218,8 +307,9 @@ struct StressletNormalDensity {
         dr2 = __builtin_fma(dy, dy, dr2);
         dr2 = __builtin_fma(dz, dz, dr2);
         const double denom2 = (dr2 < p.eps2) ? dr2 + p.reg2 : dr2;
-        double y = rsq_refined(denom2);
-        y = (dr2 == 0.0) ? 0.0 : y;
+        double y = rsq_x2(denom2);
+        if (MASKED)
+            y = (dr2 == 0.0) ? 0.0 : y;
         const double y2 = y * y;
         const double rinv5 = y * y2 * y2;
         double ddn = dx * f[0];
@@ -238,22 +328,86 @@ struct StressletNormalDensity {
 
 /* ---- driver ----------------------------------------------------------- */
 
+#ifndef SKELLY_UNROLL
+#define SKELLY_UNROLL 4
+#endif
+
+/* N doubles (N even; 0 allowed) from a 16-byte aligned LDS address. */
+template <int N>
+__device__ __forceinline__ void lds_read16(double *dst, const double *src) {
+    typedef double d2 __attribute__((ext_vector_type(2), may_alias));
+    static_assert(N % 2 == 0, "whole 16-byte vectors only");
+#pragma unroll
+    for (int i = 0; i < N / 2; ++i) {
+        const d2 v = reinterpret_cast<const d2 *>(src)[i];
+        dst[2 * i] = v.x;
+        dst[2 * i + 1] = v.y;
+    }
+}
+
+/* Sources [s, s_end) of the staged tile onto this thread's TPT targets, in
+ * source order. Unrolled by U sources: all U sources' LDS reads issue
+ * together (one lgkmcnt wait per U sources instead of several per source)
+ * and their v_rsq/refine chains interleave. */
+template <typename K, int TPT, bool MASKED>
+__device__ __forceinline__ void pair_span(const double *lds_r, const double *lds_f,
+                                          const double *lds_g, int s, const int s_end,
+                                          const double (&tp)[TPT][3], double (&acc)[TPT][3],
+                                          const typename K::Params &params, unsigned &zmin) {
+    constexpr int U = SKELLY_UNROLL;
+    constexpr int A = K::AUXDIM > 0 ? K::AUXDIM : 1;
+    /* Callers start at a multiple of U (U even), so each group of U sources
+     * begins 16-byte aligned in all three arrays: read it as 16-byte
+     * vectors, or the reads come out as ds_read2_b64 with one address
+     * register per array. */
+    static_assert(U % 2 == 0, "the 16-byte LDS reads below need an even unroll");
+    for (; s + U <= s_end; s += U) {
+        double sp[U * 3], sf[U * K::SRCDIM], sg[U * A];
+        lds_read16<U * 3>(sp, lds_r + 3 * s);
+        lds_read16<U * K::SRCDIM>(sf, lds_f + K::SRCDIM * s);
+        lds_read16<U * K::AUXDIM>(sg, lds_g + K::AUXDIM * s);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int k = 0; k < TPT; ++k)
+                K::template pair<MASKED>(tp[k], sp + 3 * u, sf + K::SRCDIM * u,
+                                         sg + K::AUXDIM * u, acc[k], params, zmin);
+    }
+    for (; s < s_end; ++s) {
+        double sp[3], sf[K::SRCDIM], sg[A];
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            sp[j] = lds_r[3 * s + j];
+#pragma unroll
+        for (int j = 0; j < K::SRCDIM; ++j)
+            sf[j] = lds_f[K::SRCDIM * s + j];
+#pragma unroll
+        for (int j = 0; j < K::AUXDIM; ++j)
+            sg[j] = lds_g[K::AUXDIM * s + j];
+#pragma unroll
+        for (int k = 0; k < TPT; ++k)
+            K::template pair<MASKED>(tp[k], sp, sf, sg, acc[k], params, zmin);
+    }
+}
+
 /* PARTIAL=false: each block sums ALL sources for its targets and writes the
  * finished (scaled) velocities. PARTIAL=true (source-split, used when small
  * target counts would underfill the 256 CUs): gridDim.y slices partition the
  * sources; block (x, y) sums slice y for target tile x into
  * u_trg[y * 3*n_trg ...] UNSCALED; reduce_partials then sums the slices in
- * fixed slice order (deterministic) and applies the finish scale. */
+ * fixed slice order (deterministic) and applies the finish scale.
+ * fastpath != 0 runs each chunk unmasked first (see the file header). */
 template <typename K, int TPT, bool PARTIAL = false>
-__global__ __launch_bounds__(BLOCK) void pair_driver(const double *__restrict__ r_src,
+__global__ __launch_bounds__(BLOCK, K::MIN_WAVES) void pair_driver(const double *__restrict__ r_src,
                                                      const double *__restrict__ f_src,
                                                      const double *__restrict__ r_trg,
                                                      double *__restrict__ u_trg,
                                                      long long n_src, long long n_trg,
-                                                     typename K::Params params) {
-    __shared__ double lds[TILE * (3 + K::SRCDIM)];
+                                                     typename K::Params params, int fastpath) {
+    __shared__ __attribute__((aligned(16))) double lds[TILE * (3 + K::SRCDIM + K::AUXDIM)];
     double *lds_r = lds;
     double *lds_f = lds + TILE * 3;
+    double *lds_g = lds + TILE * (3 + K::SRCDIM);
     const int tid = threadIdx.x;
     const long long base = (long long)blockIdx.x * (BLOCK * TPT);
 
@@ -281,52 +435,64 @@ __global__ __launch_bounds__(BLOCK) void pair_driver(const double *__restrict__ 
         __syncthreads();
         for (int i = tid; i < m * 3; i += BLOCK)
             lds_r[i] = r_src[tile0 * 3 + i];
-        for (int i = tid; i < m * K::SRCDIM; i += BLOCK)
-            lds_f[i] = f_src[tile0 * K::SRCDIM + i];
+        for (int i = tid; i < m * K::SRCDIM; i += BLOCK) {
+            const double v = f_src[tile0 * K::SRCDIM + i];
+            lds_f[i] = v;
+            if (K::AUXDIM > 0) /* AUXDIM == SRCDIM where present */
+                lds_g[i] = 0.25 * v;
+        }
         __syncthreads();
 
-        /* Unroll by U sources: all U sources' LDS reads issue together (one
-         * lgkmcnt wait per U sources instead of several per source) and
-         * their v_rsq/refine chains interleave. */
-#ifndef SKELLY_UNROLL
-#define SKELLY_UNROLL 4
-#endif
-        constexpr int U = SKELLY_UNROLL;
-        int s = 0;
-        for (; s + U <= m; s += U) {
-            double sp[U][3], sf[U][K::SRCDIM];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-                    sp[u][j] = lds_r[3 * (s + u) + j];
-#pragma unroll
-                for (int j = 0; j < K::SRCDIM; ++j)
-                    sf[u][j] = lds_f[K::SRCDIM * (s + u) + j];
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
+        unsigned zmin = ~0u;
+        if (!K::HAS_MASK) {
+            pair_span<K, TPT, false>(lds_r, lds_f, lds_g, 0, m, tp, acc, params, zmin);
+            continue;
+        }
+        static_assert(SKELLY_CHUNK % SKELLY_UNROLL == 0 && TILE % SKELLY_CHUNK == 0,
+                      "chunks must hold whole unroll groups and tile the LDS tile");
+        for (int ci = 0; ci * SKELLY_CHUNK < m; ++ci) {
+            /* a visible multiple of CHUNK keeps the b128 LDS reads provably aligned */
+            const int c0 = ci * SKELLY_CHUNK;
+            const int c1 = c0 + SKELLY_CHUNK < m ? c0 + SKELLY_CHUNK : m;
+            bool masked = !fastpath;
+            if (fastpath) {
+                double saved[TPT][3];
 #pragma unroll
                 for (int k = 0; k < TPT; ++k)
-                    K::pair(tp[k], sp[u], sf[u], acc[k], params);
-        }
-        for (; s < m; ++s) {
-            double sp[3], sf[K::SRCDIM];
 #pragma unroll
-            for (int j = 0; j < 3; ++j)
-                sp[j] = lds_r[3 * s + j];
+                    for (int j = 0; j < 3; ++j)
+                        saved[k][j] = acc[k][j];
+                zmin = ~0u;
+                pair_span<K, TPT, false>(lds_r, lds_f, lds_g, c0, c1, tp, acc, params, zmin);
+                bool hit = zmin == 0u;
+                if (K::NAN_PROBE) {
 #pragma unroll
-            for (int j = 0; j < K::SRCDIM; ++j)
-                sf[j] = lds_f[K::SRCDIM * s + j];
+                    for (int k = 0; k < TPT; ++k)
 #pragma unroll
-            for (int k = 0; k < TPT; ++k)
-                K::pair(tp[k], sp, sf, acc[k], params);
+                        for (int j = 0; j < 3; ++j)
+                            hit |= acc[k][j] != acc[k][j];
+                }
+                masked = __any(hit); /* wave-uniform */
+                if (masked) {
+#pragma unroll
+                    for (int k = 0; k < TPT; ++k)
+#pragma unroll
+                        for (int j = 0; j < 3; ++j)
+                            acc[k][j] = saved[k][j];
+                }
+            }
+            if (masked)
+                pair_span<K, TPT, true>(lds_r, lds_f, lds_g, c0, c1, tp, acc, params, zmin);
         }
     }
 
+    /* Recompute the target index from an opaque copy of tid: otherwise the
+     * prologue's 64-bit index is kept live (or spilled) across the pair loop. */
+    int tid_out = tid;
+    asm volatile("" : "+v"(tid_out));
 #pragma unroll
     for (int k = 0; k < TPT; ++k) {
-        const long long it = base + (long long)k * BLOCK + tid;
+        const long long it = base + (long long)k * BLOCK + tid_out;
         if (it < n_trg) {
             if (PARTIAL) {
                 double *p = u_trg + (long long)blockIdx.y * 3 * n_trg;
@@ -407,6 +573,34 @@ static double *persistent_ws(hipStream_t stream, size_t bytes) {
     return static_cast<double *>(e.ptr);
 }
 
+/* Unmasked fast path of the pair kernels (see the file header). Mode, from
+ * skelly_set_pair_fastpath() or else SKELLY_PAIR_FASTPATH:
+ *   0  off: the masked path everywhere (A/B measurement, identity tests);
+ *   1  auto (default): on for launches whose blocks each walk at least
+ *      PAIR_FASTPATH_MIN_SRC sources;
+ *   2  always on.
+ * Why auto: when sources and targets coincide, a wave reruns up to 2*TPT = 8
+ * chunks (its 4 x 64 consecutive targets straddle two chunks each). A full
+ * grid hides that, but small launches are latency-bound on the one source
+ * slice that holds the wave's own targets: measured on MI355X at
+ * n_src = n_trg = 5e3 / 2e4 (1667 / 2000 sources a slice) always-on was
+ * 24% / 17% SLOWER than the masked path, at 1e5 (9091 a slice) 7% faster
+ * (profiles/pair_fastpath.md). 128 chunks bound the worst-case rerun at
+ * 8/128 = 6% of the slice, under the ~8% the fast path gains. */
+static int g_pair_fastpath_override = -1; /* -1 = follow env var */
+static constexpr long long PAIR_FASTPATH_MIN_SRC = 128LL * SKELLY_CHUNK;
+
+static int pair_fastpath_mode() {
+    if (g_pair_fastpath_override >= 0)
+        return g_pair_fastpath_override;
+    static const int mode = [] {
+        const char *e = getenv("SKELLY_PAIR_FASTPATH");
+        const int v = e ? atoi(e) : 1;
+        return v < 0 ? 0 : (v > 2 ? 2 : v);
+    }();
+    return mode;
+}
+
 static inline int pick_tpt(long long n_trg) {
     /* Prefer 4 targets/thread (amortizes the per-source LDS broadcast reads
      * 4x); occupancy for small target counts is recovered by source
@@ -424,6 +618,8 @@ hipError_t launch_pair(const double *r_src, const double *f_src, const double *r
                        typename K::Params params, hipStream_t stream) {
     if (n_trg <= 0)
         return hipSuccess;
+    /* the kernels accumulate ACC_FOLD x the sum (power of two: exact) */
+    params.scale /= K::ACC_FOLD;
     const int tpt = pick_tpt(n_trg);
     const long long blocks = (n_trg + (long long)BLOCK * tpt - 1) / ((long long)BLOCK * tpt);
 
@@ -444,21 +640,25 @@ hipError_t launch_pair(const double *r_src, const double *f_src, const double *r
             n_slices = 1;
     }
 
+    const int mode = pair_fastpath_mode();
+    const long long src_per_block = (n_src + n_slices - 1) / n_slices;
+    const int fast = mode == 2 || (mode == 1 && src_per_block >= PAIR_FASTPATH_MIN_SRC);
+
     dim3 block(BLOCK);
     if (n_slices == 1) {
         dim3 grid((unsigned)blocks);
         switch (tpt) {
         case 4:
             hipLaunchKernelGGL((pair_driver<K, 4>), grid, block, 0, stream, r_src, f_src,
-                               r_trg, u_trg, n_src, n_trg, params);
+                               r_trg, u_trg, n_src, n_trg, params, fast);
             break;
         case 2:
             hipLaunchKernelGGL((pair_driver<K, 2>), grid, block, 0, stream, r_src, f_src,
-                               r_trg, u_trg, n_src, n_trg, params);
+                               r_trg, u_trg, n_src, n_trg, params, fast);
             break;
         default:
             hipLaunchKernelGGL((pair_driver<K, 1>), grid, block, 0, stream, r_src, f_src,
-                               r_trg, u_trg, n_src, n_trg, params);
+                               r_trg, u_trg, n_src, n_trg, params, fast);
             break;
         }
         return hipGetLastError();
@@ -481,15 +681,15 @@ hipError_t launch_pair(const double *r_src, const double *f_src, const double *r
     switch (tpt) {
     case 4:
         hipLaunchKernelGGL((pair_driver<K, 4, true>), grid, block, 0, stream, r_src, f_src,
-                           r_trg, workspace, n_src, n_trg, params);
+                           r_trg, workspace, n_src, n_trg, params, fast);
         break;
     case 2:
         hipLaunchKernelGGL((pair_driver<K, 2, true>), grid, block, 0, stream, r_src, f_src,
-                           r_trg, workspace, n_src, n_trg, params);
+                           r_trg, workspace, n_src, n_trg, params, fast);
         break;
     default:
         hipLaunchKernelGGL((pair_driver<K, 1, true>), grid, block, 0, stream, r_src, f_src,
-                           r_trg, workspace, n_src, n_trg, params);
+                           r_trg, workspace, n_src, n_trg, params, fast);
         break;
     }
     const long long rblocks = (3 * n_trg + BLOCK - 1) / BLOCK;
@@ -705,4 +905,10 @@ hipError_t run_fp64_peak(double *out_tflops) {
  * UNCAPTURED warmup pass, so capture itself allocates nothing. */
 extern "C" void skelly_set_persistent_ws(int on) {
     skelly::g_persistent_ws_override = on;
+}
+
+/* Runtime override of the unmasked pair fast path: 0 off, 1 auto, 2 always
+ * (see pair_fastpath_mode above). Results do not depend on it. */
+extern "C" void skelly_set_pair_fastpath(int mode) {
+    skelly::g_pair_fastpath_override = mode < 0 ? 0 : (mode > 2 ? 2 : mode);
 }
