@@ -119,6 +119,49 @@ inline MatrixXd rotlet(const CMatrixRef &r_src, const CMatrixRef &r_trg,
     return u;
 }
 
+/* Velocity gradients of the four fields above (no reference counterpart):
+ * 9 x n_trg, column t holding G[i][j] = du_i/dx_j at target t in row-major
+ * order (row 3*i + j), fully scaled like the velocities. */
+inline MatrixXd stokeslet_grad(const CMatrixRef &r_src, const CMatrixRef &r_trg,
+                               const CMatrixRef &f_src, double eta) {
+    MatrixXd g(9, r_trg.size() / 3);
+    check_rc(skelly_stokeslet_grad_host(r_src.ptr, f_src.ptr, r_src.size() / 3, r_trg.ptr,
+                                        g.data(), r_trg.size() / 3, eta),
+             "stokeslet_grad");
+    return g;
+}
+
+inline MatrixXd stresslet_grad(const CMatrixRef &r_src, const CMatrixRef &r_trg,
+                               const CMatrixRef &f_src, double eta) {
+    MatrixXd g(9, r_trg.size() / 3);
+    check_rc(skelly_stresslet_grad_host(r_src.ptr, f_src.ptr, r_src.size() / 3, r_trg.ptr,
+                                        g.data(), r_trg.size() / 3, eta),
+             "stresslet_grad");
+    return g;
+}
+
+inline MatrixXd oseen_tensor_contract_grad(const CMatrixRef &r_src, const CMatrixRef &r_trg,
+                                           const CMatrixRef &density, double eta,
+                                           double reg = 5e-3, double epsilon_distance = 1e-5) {
+    MatrixXd g(9, r_trg.size() / 3);
+    check_rc(skelly_oseen_contract_grad_host(r_src.ptr, r_trg.ptr, density.ptr, g.data(),
+                                             r_src.size() / 3, r_trg.size() / 3, eta, reg,
+                                             epsilon_distance),
+             "oseen_tensor_contract_grad");
+    return g;
+}
+
+inline MatrixXd rotlet_grad(const CMatrixRef &r_src, const CMatrixRef &r_trg,
+                            const CMatrixRef &density, double eta, double reg = 5e-3,
+                            double epsilon_distance = 1e-5) {
+    MatrixXd g(9, r_trg.size() / 3);
+    check_rc(skelly_rotlet_grad_host(r_src.ptr, r_trg.ptr, density.ptr, g.data(),
+                                     r_src.size() / 3, r_trg.size() / 3, eta, reg,
+                                     epsilon_distance),
+             "rotlet_grad");
+    return g;
+}
+
 /* Mirror of the reference's string-keyed backend selection
  * (fiber_container_base.cpp:20-33, periphery.cpp:337-352): "HIP" is this
  * engine; the reference's "CPU"/"FMM" backends are out of scope. */

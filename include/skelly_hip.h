@@ -125,6 +125,43 @@ int skelly_rotlet_device(const double *d_r_src, const double *d_r_trg,
                          long long n_src, long long n_trg,
                          double eta, double reg, double epsilon_distance, void *stream);
 
+/* ---- velocity gradients (analytic, one pass) ----
+ *
+ * G[i][j] = d u_i / d x_j of the matching velocity entry point, differentiated
+ * at the target: g_trg is double[9 * n_trg], row-major per target
+ * (G[i][j] at 9*it + 3*i + j), overwritten, fully scaled (1/(8*pi*eta)).
+ * Argument order and error contract are those of the velocity forms. Each
+ * formula is the exact derivative inside each branch of its kernel:
+ * coincident pairs contribute zero for stokeslet/stresslet/oseen, pairs
+ * under epsilon_distance differentiate the regularized expression. Results
+ * are bit-reproducible and independent of skelly_set_pair_fastpath. */
+int skelly_stokeslet_grad_host(const double *r_src, const double *f_src, long long n_src,
+                               const double *r_trg, double *g_trg, long long n_trg, double eta);
+int skelly_stresslet_grad_host(const double *r_src, const double *f_src, long long n_src,
+                               const double *r_trg, double *g_trg, long long n_trg, double eta);
+int skelly_oseen_contract_grad_host(const double *r_src, const double *r_trg,
+                                    const double *density, double *g_trg,
+                                    long long n_src, long long n_trg,
+                                    double eta, double reg, double epsilon_distance);
+int skelly_rotlet_grad_host(const double *r_src, const double *r_trg, const double *density,
+                            double *g_trg, long long n_src, long long n_trg,
+                            double eta, double reg, double epsilon_distance);
+int skelly_stokeslet_grad_device(const double *d_r_src, const double *d_f_src, long long n_src,
+                                 const double *d_r_trg, double *d_g_trg, long long n_trg,
+                                 double eta, void *stream);
+int skelly_stresslet_grad_device(const double *d_r_src, const double *d_f_src, long long n_src,
+                                 const double *d_r_trg, double *d_g_trg, long long n_trg,
+                                 double eta, void *stream);
+int skelly_oseen_contract_grad_device(const double *d_r_src, const double *d_r_trg,
+                                      const double *d_density, double *d_g_trg,
+                                      long long n_src, long long n_trg,
+                                      double eta, double reg, double epsilon_distance,
+                                      void *stream);
+int skelly_rotlet_grad_device(const double *d_r_src, const double *d_r_trg,
+                              const double *d_density, double *d_g_trg,
+                              long long n_src, long long n_trg,
+                              double eta, double reg, double epsilon_distance, void *stream);
+
 /* Contraction of the stresslet with a normal and a density field over one
  * point set (kernels::stresslet_times_normal_times_density,
  * src/core/kernels.cpp:307-334; no eta dependence, factor -3/(4*pi)):

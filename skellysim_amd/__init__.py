@@ -26,6 +26,14 @@ from .evaluator import (  # noqa: F401
     stresslet_normal_density_device,
     stresslet_times_normal_device,
     oseen_tensor_batched_device,
+    stokeslet_grad,
+    stresslet_grad,
+    oseen_contract_grad,
+    rotlet_grad,
+    stokeslet_grad_device,
+    stresslet_grad_device,
+    oseen_contract_grad_device,
+    rotlet_grad_device,
 )
 from .sharded import ShardedPairEvaluator, shard_sizes, allgather_rows  # noqa: F401
 

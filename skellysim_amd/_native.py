@@ -42,6 +42,14 @@ def _bind(lib):
                                                  ctypes.c_double, pv]
     lib.skelly_rotlet_device.argtypes = [pv, pv, pv, pv, _LL, _LL,
                                          ctypes.c_double, ctypes.c_double, ctypes.c_double, pv]
+    lib.skelly_stokeslet_grad_host.argtypes = lib.skelly_stokeslet_host.argtypes
+    lib.skelly_stresslet_grad_host.argtypes = lib.skelly_stresslet_host.argtypes
+    lib.skelly_oseen_contract_grad_host.argtypes = lib.skelly_oseen_contract_host.argtypes
+    lib.skelly_rotlet_grad_host.argtypes = lib.skelly_rotlet_host.argtypes
+    lib.skelly_stokeslet_grad_device.argtypes = lib.skelly_stokeslet_device.argtypes
+    lib.skelly_stresslet_grad_device.argtypes = lib.skelly_stresslet_device.argtypes
+    lib.skelly_oseen_contract_grad_device.argtypes = lib.skelly_oseen_contract_device.argtypes
+    lib.skelly_rotlet_grad_device.argtypes = lib.skelly_rotlet_device.argtypes
     lib.skelly_stresslet_normal_density_host.argtypes = [_DP, _DP, _DP, _DP, _LL,
                                                           ctypes.c_double, ctypes.c_double]
     lib.skelly_stresslet_normal_density_device.argtypes = [pv, pv, pv, pv, _LL, _LL,

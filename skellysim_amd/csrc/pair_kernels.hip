@@ -41,6 +41,8 @@
  *   - Small target counts (< 512 workgroups at one target/thread) switch to
  *     a source-split launch: gridDim.y source slices accumulate partials
  *     that a second kernel reduces in fixed slice order (deterministic).
+ *   - The same driver evaluates the analytic velocity gradients of the four
+ *     kernels (9 outputs a target, K::OUTDIM; functors further down).
  *
  * Roofline: compute-bound on the fp64 VALU. The kernels are
  * deliberately not GEMM-shaped: gfx950's fp64 matrix rate equals its vector
@@ -61,6 +63,11 @@
  * SKELLY_UNROLL, divides TILE). Measured on MI355X, profiles/pair_fastpath.md. */
 #ifndef SKELLY_CHUNK
 #define SKELLY_CHUNK 64
+#endif
+
+/* Sources per unrolled group of the velocity kernels' pair loop (even). */
+#ifndef SKELLY_UNROLL
+#define SKELLY_UNROLL 4
 #endif
 
 /* R = 2/sqrt(x): v_rsq_f64 + one refinement step with the constant factor
@@ -102,9 +109,21 @@ __device__ inline double rsq_refined(double x) { return 0.5 * rsq_x2(x); }
  *              select out and must make a coincident pair detectable.
  *   NAN_PROBE  an unmasked coincident pair turns the accumulators NaN
  *              (else pair<false> lowers `zmin` to 0 on one).
- *   AUXDIM     doubles per source of the second LDS copy g = f/4 (0: none). */
+ *   AUXDIM     doubles per source of the second LDS copy g = f/4 (0: none).
+ *   OUTDIM     accumulators and outputs per target (3 velocity components,
+ *              9 for the gradient functors further down).
+ *   MAX_TPT    most targets a thread holds (register budget).
+ *   UNROLL     sources per unrolled group of the pair loop (even).
+ *   FASTPATH   the unmasked chunk-rerun path is wired (needs HAS_MASK). */
 
-struct Stokeslet {
+struct VelocityTraits {
+    static constexpr int OUTDIM = 3;
+    static constexpr int MAX_TPT = 4;
+    static constexpr int UNROLL = SKELLY_UNROLL;
+    static constexpr bool FASTPATH = true;
+};
+
+struct Stokeslet : VelocityTraits {
     static constexpr int MIN_WAVES = 3;
     static constexpr int SRCDIM = 3;
     static constexpr int AUXDIM = 3;
@@ -142,7 +161,7 @@ struct Stokeslet {
     __device__ static inline double finish(double a, const Params &p) { return a * p.scale; }
 };
 
-struct Stresslet {
+struct Stresslet : VelocityTraits {
     static constexpr int MIN_WAVES = 2;
     static constexpr int SRCDIM = 9;
     static constexpr int AUXDIM = 0;
@@ -184,7 +203,7 @@ struct Stresslet {
     __device__ static inline double finish(double a, const Params &p) { return a * p.scale; }
 };
 
-struct OseenContract {
+struct OseenContract : VelocityTraits {
     static constexpr int MIN_WAVES = 3;
     static constexpr int SRCDIM = 3;
     static constexpr int AUXDIM = 3;
@@ -238,7 +257,7 @@ struct OseenContract {
     __device__ static inline double finish(double a, const Params &p) { return a * p.scale; }
 };
 
-struct Rotlet {
+struct Rotlet : VelocityTraits {
     static constexpr int MIN_WAVES = 3;
     static constexpr int SRCDIM = 3;
     static constexpr int AUXDIM = 0;
@@ -277,7 +296,7 @@ struct Rotlet {
     __device__ static inline double finish(double a, const Params &p) { return a * p.scale; }
 };
 
-struct StressletNormalDensity {
+struct StressletNormalDensity : VelocityTraits {
     static constexpr int MIN_WAVES = 3;
     static constexpr int SRCDIM = 6; /* normal[3] + density[3] per source */
     static constexpr int AUXDIM = 0;
@@ -326,11 +345,190 @@ struct StressletNormalDensity {
     __device__ static inline double finish(double a, const Params &p) { return a * p.scale; }
 };
 
-/* ---- driver ----------------------------------------------------------- */
+/* ---- velocity-gradient functors ----------------------------------------
+ * G[i][j] = d u_i / d x_j at the target, 9 accumulators per target stored
+ * row-major (acc[3*i + j]); d = t - s, y = 1/sqrt(den), R = 2y from rsq_x2.
+ * Each formula is the exact derivative of the matching velocity kernel inside
+ * each of its branches (the regularized branches differentiate the
+ * regularized expression). Nine accumulators a target leave room for fewer
+ * targets per thread and a shorter unroll than the velocity kernels
+ * (MAX_TPT, UNROLL; numbers in DESIGN.md), and every pair goes through the
+ * r == 0 mask (FASTPATH off), so the result cannot depend on
+ * skelly_set_pair_fastpath. */
 
-#ifndef SKELLY_UNROLL
-#define SKELLY_UNROLL 4
+#ifndef SKELLY_GRAD_TPT
+#define SKELLY_GRAD_TPT 2
 #endif
+#ifndef SKELLY_DLGRAD_TPT
+#define SKELLY_DLGRAD_TPT 2
+#endif
+
+struct GradTraits {
+    static constexpr int OUTDIM = 9;
+    static constexpr int UNROLL = 2;
+    static constexpr int AUXDIM = 0;
+    static constexpr bool FASTPATH = false;
+    static constexpr bool NAN_PROBE = false;
+};
+
+/* Stokeslet and regularized Oseen in one functor: Params{., 0, 0} is the
+ * plain Stokeslet (den = r^2), else den follows OseenContract::pair.
+ *   u_i  = y f_i + y^3 (f.d) d_i
+ *   G_ij = y^3 (d_i f_j - f_i d_j + (f.d) delta_ij) - 3 y^5 (f.d) d_i d_j
+ * With R^3 = 8 y^3 and -3 y^2 = -0.75 R^2 every term is 8x the plain one. */
+struct StokesletGrad : GradTraits {
+    static constexpr int MIN_WAVES = 3;
+    static constexpr int MAX_TPT = SKELLY_GRAD_TPT;
+    static constexpr int SRCDIM = 3;
+    static constexpr bool HAS_MASK = true;
+    static constexpr double ACC_FOLD = 8.0;
+    struct Params {
+        double scale; /* 1/(8*pi*eta) / ACC_FOLD */
+        double reg2;
+        double eps2;
+    };
+    template <bool MASKED>
+    __device__ static inline void pair(const double t[3], const double sp[3], const double f[3],
+                                       const double *, double acc[9], const Params &p,
+                                       unsigned &) {
+        const double dx = t[0] - sp[0];
+        const double dy = t[1] - sp[1];
+        const double dz = t[2] - sp[2];
+        double r2 = dx * dx;
+        r2 = __builtin_fma(dy, dy, r2);
+        r2 = __builtin_fma(dz, dz, r2);
+        const double den = (r2 > p.eps2) ? r2 : r2 + p.reg2;
+        double R = rsq_x2(den);
+        if (MASKED)
+            R = (r2 == 0.0) ? 0.0 : R;
+        const double R2 = R * R;
+        const double R3 = R2 * R;
+        double fd = f[0] * dx;
+        fd = __builtin_fma(f[1], dy, fd);
+        fd = __builtin_fma(f[2], dz, fd);
+        const double A = fd * R3;            /* 8 y^3 (f.d) */
+        const double B = A * (-0.75 * R2);   /* -8 * 3 y^5 (f.d) */
+        const double Bdx = B * dx, Bdy = B * dy, Bdz = B * dz;
+        const double Rfx = R3 * f[0], Rfy = R3 * f[1], Rfz = R3 * f[2];
+        const double vx = Bdx + Rfx, vy = Bdy + Rfy, vz = Bdz + Rfz;
+        /* diagonal: the antisymmetric part cancels exactly */
+        acc[0] = __builtin_fma(Bdx, dx, acc[0]) + A;
+        acc[4] = __builtin_fma(Bdy, dy, acc[4]) + A;
+        acc[8] = __builtin_fma(Bdz, dz, acc[8]) + A;
+        /* off-diagonal: d_i (B d_j + R3 f_j) - (R3 f_i) d_j */
+        acc[1] = __builtin_fma(-Rfx, dy, __builtin_fma(dx, vy, acc[1]));
+        acc[2] = __builtin_fma(-Rfx, dz, __builtin_fma(dx, vz, acc[2]));
+        acc[3] = __builtin_fma(-Rfy, dx, __builtin_fma(dy, vx, acc[3]));
+        acc[5] = __builtin_fma(-Rfy, dz, __builtin_fma(dy, vz, acc[5]));
+        acc[6] = __builtin_fma(-Rfz, dx, __builtin_fma(dz, vx, acc[6]));
+        acc[7] = __builtin_fma(-Rfz, dy, __builtin_fma(dz, vy, acc[7]));
+    }
+    __device__ static inline double finish(double a, const Params &p) { return a * p.scale; }
+};
+
+/* Stresslet: S_kl = f[3k+l], C = d_k S_kl d_l, b_j = (S_jl + S_lj) d_l.
+ *   G_ij = -3 [ y^5 (d_i b_j + C delta_ij) - 5 y^7 C d_i d_j ]
+ * The accumulators hold 32x the bracket (R^5 = 32 y^5, -5 y^2 = -1.25 R^2);
+ * the -3 rides in Params::scale. b.d = 2C. */
+struct StressletGrad : GradTraits {
+    static constexpr int MIN_WAVES = 3;
+    static constexpr int MAX_TPT = SKELLY_DLGRAD_TPT;
+    static constexpr int SRCDIM = 9;
+    static constexpr bool HAS_MASK = true;
+    static constexpr double ACC_FOLD = 32.0;
+    struct Params {
+        double scale; /* -3/(8*pi*eta) / ACC_FOLD */
+    };
+    template <bool MASKED>
+    __device__ static inline void pair(const double t[3], const double sp[3], const double f[9],
+                                       const double *, double acc[9], const Params &,
+                                       unsigned &) {
+        const double dx = t[0] - sp[0];
+        const double dy = t[1] - sp[1];
+        const double dz = t[2] - sp[2];
+        double r2 = dx * dx;
+        r2 = __builtin_fma(dy, dy, r2);
+        r2 = __builtin_fma(dz, dz, r2);
+        double R = rsq_x2(r2);
+        if (MASKED)
+            R = (r2 == 0.0) ? 0.0 : R;
+        const double R2 = R * R;
+        const double R5 = R * R2 * R2;
+        const double txy = f[1] + f[3], txz = f[2] + f[6], tyz = f[5] + f[7];
+        const double px = f[0] * dx, py = f[4] * dy, pz = f[8] * dz;
+        const double bx = __builtin_fma(txy, dy, __builtin_fma(txz, dz, px + px));
+        const double by = __builtin_fma(txy, dx, __builtin_fma(tyz, dz, py + py));
+        const double bz = __builtin_fma(txz, dx, __builtin_fma(tyz, dy, pz + pz));
+        double c2 = bx * dx;
+        c2 = __builtin_fma(by, dy, c2);
+        c2 = __builtin_fma(bz, dz, c2);
+        const double A = c2 * (0.5 * R5);    /* 32 y^5 C */
+        const double Bq = A * (-1.25 * R2);  /* -32 * 5 y^7 C */
+        const double vx = __builtin_fma(Bq, dx, R5 * bx);
+        const double vy = __builtin_fma(Bq, dy, R5 * by);
+        const double vz = __builtin_fma(Bq, dz, R5 * bz);
+        acc[0] = __builtin_fma(dx, vx, acc[0]) + A;
+        acc[1] = __builtin_fma(dx, vy, acc[1]);
+        acc[2] = __builtin_fma(dx, vz, acc[2]);
+        acc[3] = __builtin_fma(dy, vx, acc[3]);
+        acc[4] = __builtin_fma(dy, vy, acc[4]) + A;
+        acc[5] = __builtin_fma(dy, vz, acc[5]);
+        acc[6] = __builtin_fma(dz, vx, acc[6]);
+        acc[7] = __builtin_fma(dz, vy, acc[7]);
+        acc[8] = __builtin_fma(dz, vz, acc[8]) + A;
+    }
+    __device__ static inline double finish(double a, const Params &p) { return a * p.scale; }
+};
+
+/* Rotlet: c = rho x d in Rotlet::pair's sign convention, den as there (no
+ * zero mask).
+ *   u_i  = y^3 c_i
+ *   G_ij = y^3 eps_ikj rho_k - 3 y^5 c_i d_j          (accumulated 8x) */
+struct RotletGrad : GradTraits {
+    static constexpr int MIN_WAVES = 3;
+    static constexpr int MAX_TPT = SKELLY_GRAD_TPT;
+    static constexpr int SRCDIM = 3;
+    static constexpr bool HAS_MASK = false;
+    static constexpr double ACC_FOLD = 8.0;
+    struct Params {
+        double scale; /* 1/(8*pi*eta) / ACC_FOLD */
+        double reg2;
+        double eps2;
+    };
+    template <bool MASKED>
+    __device__ static inline void pair(const double t[3], const double sp[3], const double rho[3],
+                                       const double *, double acc[9], const Params &p,
+                                       unsigned &) {
+        const double dx = t[0] - sp[0];
+        const double dy = t[1] - sp[1];
+        const double dz = t[2] - sp[2];
+        double r2 = dx * dx;
+        r2 = __builtin_fma(dy, dy, r2);
+        r2 = __builtin_fma(dz, dz, r2);
+        const double den = (r2 < p.eps2) ? r2 + p.reg2 : r2;
+        const double R = rsq_x2(den);
+        const double R2 = R * R;
+        const double R3 = R2 * R;
+        const double q = (-0.75 * R2) * R3; /* -8 * 3 y^5 */
+        const double cx = __builtin_fma(dz, rho[1], -(dy * rho[2]));
+        const double cy = __builtin_fma(dx, rho[2], -(dz * rho[0]));
+        const double cz = __builtin_fma(dy, rho[0], -(dx * rho[1]));
+        const double qx = q * cx, qy = q * cy, qz = q * cz;
+        const double wx = R3 * rho[0], wy = R3 * rho[1], wz = R3 * rho[2];
+        acc[0] = __builtin_fma(qx, dx, acc[0]);
+        acc[1] = __builtin_fma(qx, dy, acc[1]) - wz;
+        acc[2] = __builtin_fma(qx, dz, acc[2]) + wy;
+        acc[3] = __builtin_fma(qy, dx, acc[3]) + wz;
+        acc[4] = __builtin_fma(qy, dy, acc[4]);
+        acc[5] = __builtin_fma(qy, dz, acc[5]) - wx;
+        acc[6] = __builtin_fma(qz, dx, acc[6]) - wy;
+        acc[7] = __builtin_fma(qz, dy, acc[7]) + wx;
+        acc[8] = __builtin_fma(qz, dz, acc[8]);
+    }
+    __device__ static inline double finish(double a, const Params &p) { return a * p.scale; }
+};
+
+/* ---- driver ----------------------------------------------------------- */
 
 /* N doubles (N even; 0 allowed) from a 16-byte aligned LDS address. */
 template <int N>
@@ -352,9 +550,10 @@ __device__ __forceinline__ void lds_read16(double *dst, const double *src) {
 template <typename K, int TPT, bool MASKED>
 __device__ __forceinline__ void pair_span(const double *lds_r, const double *lds_f,
                                           const double *lds_g, int s, const int s_end,
-                                          const double (&tp)[TPT][3], double (&acc)[TPT][3],
+                                          const double (&tp)[TPT][3],
+                                          double (&acc)[TPT][K::OUTDIM],
                                           const typename K::Params &params, unsigned &zmin) {
-    constexpr int U = SKELLY_UNROLL;
+    constexpr int U = K::UNROLL;
     constexpr int A = K::AUXDIM > 0 ? K::AUXDIM : 1;
     /* Callers start at a multiple of U (U even), so each group of U sources
      * begins 16-byte aligned in all three arrays: read it as 16-byte
@@ -394,7 +593,7 @@ __device__ __forceinline__ void pair_span(const double *lds_r, const double *lds
  * finished (scaled) velocities. PARTIAL=true (source-split, used when small
  * target counts would underfill the 256 CUs): gridDim.y slices partition the
  * sources; block (x, y) sums slice y for target tile x into
- * u_trg[y * 3*n_trg ...] UNSCALED; reduce_partials then sums the slices in
+ * u_trg[y * OUTDIM*n_trg ...] UNSCALED; reduce_partials then sums the slices in
  * fixed slice order (deterministic) and applies the finish scale.
  * fastpath != 0 runs each chunk unmasked first (see the file header). */
 template <typename K, int TPT, bool PARTIAL = false>
@@ -412,7 +611,8 @@ __global__ __launch_bounds__(BLOCK, K::MIN_WAVES) void pair_driver(const double 
     const long long base = (long long)blockIdx.x * (BLOCK * TPT);
 
     double tp[TPT][3];
-    double acc[TPT][3];
+    constexpr int OD = K::OUTDIM;
+    double acc[TPT][OD];
 #pragma unroll
     for (int k = 0; k < TPT; ++k) {
         long long it = base + (long long)k * BLOCK + tid;
@@ -420,7 +620,9 @@ __global__ __launch_bounds__(BLOCK, K::MIN_WAVES) void pair_driver(const double 
         tp[k][0] = r_trg[3 * itc + 0];
         tp[k][1] = r_trg[3 * itc + 1];
         tp[k][2] = r_trg[3 * itc + 2];
-        acc[k][0] = acc[k][1] = acc[k][2] = 0.0;
+#pragma unroll
+        for (int j = 0; j < OD; ++j)
+            acc[k][j] = 0.0;
     }
 
     long long src_begin = 0, src_end = n_src;
@@ -444,11 +646,12 @@ __global__ __launch_bounds__(BLOCK, K::MIN_WAVES) void pair_driver(const double 
         __syncthreads();
 
         unsigned zmin = ~0u;
-        if (!K::HAS_MASK) {
-            pair_span<K, TPT, false>(lds_r, lds_f, lds_g, 0, m, tp, acc, params, zmin);
+        if (!K::HAS_MASK || !K::FASTPATH) {
+            /* no mask to skip, or always through it: one span over the tile */
+            pair_span<K, TPT, K::HAS_MASK>(lds_r, lds_f, lds_g, 0, m, tp, acc, params, zmin);
             continue;
         }
-        static_assert(SKELLY_CHUNK % SKELLY_UNROLL == 0 && TILE % SKELLY_CHUNK == 0,
+        static_assert(SKELLY_CHUNK % K::UNROLL == 0 && TILE % SKELLY_CHUNK == 0,
                       "chunks must hold whole unroll groups and tile the LDS tile");
         for (int ci = 0; ci * SKELLY_CHUNK < m; ++ci) {
             /* a visible multiple of CHUNK keeps the b128 LDS reads provably aligned */
@@ -456,11 +659,11 @@ __global__ __launch_bounds__(BLOCK, K::MIN_WAVES) void pair_driver(const double 
             const int c1 = c0 + SKELLY_CHUNK < m ? c0 + SKELLY_CHUNK : m;
             bool masked = !fastpath;
             if (fastpath) {
-                double saved[TPT][3];
+                double saved[TPT][OD];
 #pragma unroll
                 for (int k = 0; k < TPT; ++k)
 #pragma unroll
-                    for (int j = 0; j < 3; ++j)
+                    for (int j = 0; j < OD; ++j)
                         saved[k][j] = acc[k][j];
                 zmin = ~0u;
                 pair_span<K, TPT, false>(lds_r, lds_f, lds_g, c0, c1, tp, acc, params, zmin);
@@ -469,7 +672,7 @@ __global__ __launch_bounds__(BLOCK, K::MIN_WAVES) void pair_driver(const double 
 #pragma unroll
                     for (int k = 0; k < TPT; ++k)
 #pragma unroll
-                        for (int j = 0; j < 3; ++j)
+                        for (int j = 0; j < OD; ++j)
                             hit |= acc[k][j] != acc[k][j];
                 }
                 masked = __any(hit); /* wave-uniform */
@@ -477,7 +680,7 @@ __global__ __launch_bounds__(BLOCK, K::MIN_WAVES) void pair_driver(const double 
 #pragma unroll
                     for (int k = 0; k < TPT; ++k)
 #pragma unroll
-                        for (int j = 0; j < 3; ++j)
+                        for (int j = 0; j < OD; ++j)
                             acc[k][j] = saved[k][j];
                 }
             }
@@ -495,32 +698,33 @@ __global__ __launch_bounds__(BLOCK, K::MIN_WAVES) void pair_driver(const double 
         const long long it = base + (long long)k * BLOCK + tid_out;
         if (it < n_trg) {
             if (PARTIAL) {
-                double *p = u_trg + (long long)blockIdx.y * 3 * n_trg;
-                p[3 * it + 0] = acc[k][0];
-                p[3 * it + 1] = acc[k][1];
-                p[3 * it + 2] = acc[k][2];
+                double *p = u_trg + (long long)blockIdx.y * OD * n_trg;
+#pragma unroll
+                for (int j = 0; j < OD; ++j)
+                    p[OD * it + j] = acc[k][j];
             } else {
-                u_trg[3 * it + 0] = K::finish(acc[k][0], params);
-                u_trg[3 * it + 1] = K::finish(acc[k][1], params);
-                u_trg[3 * it + 2] = K::finish(acc[k][2], params);
+#pragma unroll
+                for (int j = 0; j < OD; ++j)
+                    u_trg[OD * it + j] = K::finish(acc[k][j], params);
             }
         }
     }
 }
 
 /* Sum source-slice partials in fixed slice order and apply the finish scale.
- * partial layout: [n_slices][n_trg][3]; one thread per (target, component). */
+ * partial layout: [n_slices][n_trg][OUTDIM]; one thread per (target, component). */
 template <typename K>
 __global__ __launch_bounds__(BLOCK) void reduce_partials(const double *__restrict__ partial,
                                                          double *__restrict__ u_trg,
                                                          long long n_trg, int n_slices,
                                                          typename K::Params params) {
-    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; /* 3*n_trg elems */
-    if (i >= 3 * n_trg)
+    const long long n_out = K::OUTDIM * n_trg;
+    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n_out)
         return;
     double s = 0.0;
     for (int y = 0; y < n_slices; ++y)
-        s += partial[(long long)y * 3 * n_trg + i];
+        s += partial[(long long)y * n_out + i];
     u_trg[i] = K::finish(s, params);
 }
 
@@ -601,13 +805,14 @@ static int pair_fastpath_mode() {
     return mode;
 }
 
+template <typename K>
 static inline int pick_tpt(long long n_trg) {
     /* Prefer 4 targets/thread (amortizes the per-source LDS broadcast reads
-     * 4x); occupancy for small target counts is recovered by source
-     * splitting, not by shrinking TPT. */
-    if (n_trg >= BLOCK * 4)
+     * 4x), up to what the functor's registers hold; occupancy for small
+     * target counts is recovered by source splitting, not by shrinking TPT. */
+    if (K::MAX_TPT >= 4 && n_trg >= BLOCK * 4)
         return 4;
-    if (n_trg >= BLOCK * 2)
+    if (K::MAX_TPT >= 2 && n_trg >= BLOCK * 2)
         return 2;
     return 1;
 }
@@ -620,7 +825,7 @@ hipError_t launch_pair(const double *r_src, const double *f_src, const double *r
         return hipSuccess;
     /* the kernels accumulate ACC_FOLD x the sum (power of two: exact) */
     params.scale /= K::ACC_FOLD;
-    const int tpt = pick_tpt(n_trg);
+    const int tpt = pick_tpt<K>(n_trg);
     const long long blocks = (n_trg + (long long)BLOCK * tpt - 1) / ((long long)BLOCK * tpt);
 
     /* Source-split when the target grid alone underfills the chip (256 CUs;
@@ -649,12 +854,14 @@ hipError_t launch_pair(const double *r_src, const double *f_src, const double *r
         dim3 grid((unsigned)blocks);
         switch (tpt) {
         case 4:
-            hipLaunchKernelGGL((pair_driver<K, 4>), grid, block, 0, stream, r_src, f_src,
-                               r_trg, u_trg, n_src, n_trg, params, fast);
+            if constexpr (K::MAX_TPT >= 4)
+                hipLaunchKernelGGL((pair_driver<K, 4>), grid, block, 0, stream, r_src, f_src,
+                                   r_trg, u_trg, n_src, n_trg, params, fast);
             break;
         case 2:
-            hipLaunchKernelGGL((pair_driver<K, 2>), grid, block, 0, stream, r_src, f_src,
-                               r_trg, u_trg, n_src, n_trg, params, fast);
+            if constexpr (K::MAX_TPT >= 2)
+                hipLaunchKernelGGL((pair_driver<K, 2>), grid, block, 0, stream, r_src, f_src,
+                                   r_trg, u_trg, n_src, n_trg, params, fast);
             break;
         default:
             hipLaunchKernelGGL((pair_driver<K, 1>), grid, block, 0, stream, r_src, f_src,
@@ -667,7 +874,7 @@ hipError_t launch_pair(const double *r_src, const double *f_src, const double *r
     /* split path: same TPT, gridDim.y source slices into a partial buffer */
     double *workspace = nullptr;
     bool pooled = false;
-    const size_t ws_bytes = (size_t)n_slices * 3 * n_trg * sizeof(double);
+    const size_t ws_bytes = (size_t)n_slices * K::OUTDIM * n_trg * sizeof(double);
     if (persistent_ws_enabled()) {
         workspace = persistent_ws(stream, ws_bytes);
         pooled = workspace != nullptr;
@@ -680,19 +887,21 @@ hipError_t launch_pair(const double *r_src, const double *f_src, const double *r
     dim3 grid((unsigned)blocks, (unsigned)n_slices);
     switch (tpt) {
     case 4:
-        hipLaunchKernelGGL((pair_driver<K, 4, true>), grid, block, 0, stream, r_src, f_src,
-                           r_trg, workspace, n_src, n_trg, params, fast);
+        if constexpr (K::MAX_TPT >= 4)
+            hipLaunchKernelGGL((pair_driver<K, 4, true>), grid, block, 0, stream, r_src, f_src,
+                               r_trg, workspace, n_src, n_trg, params, fast);
         break;
     case 2:
-        hipLaunchKernelGGL((pair_driver<K, 2, true>), grid, block, 0, stream, r_src, f_src,
-                           r_trg, workspace, n_src, n_trg, params, fast);
+        if constexpr (K::MAX_TPT >= 2)
+            hipLaunchKernelGGL((pair_driver<K, 2, true>), grid, block, 0, stream, r_src, f_src,
+                               r_trg, workspace, n_src, n_trg, params, fast);
         break;
     default:
         hipLaunchKernelGGL((pair_driver<K, 1, true>), grid, block, 0, stream, r_src, f_src,
                            r_trg, workspace, n_src, n_trg, params, fast);
         break;
     }
-    const long long rblocks = (3 * n_trg + BLOCK - 1) / BLOCK;
+    const long long rblocks = (K::OUTDIM * n_trg + BLOCK - 1) / BLOCK;
     hipLaunchKernelGGL((reduce_partials<K>), dim3((unsigned)rblocks), block, 0, stream,
                        workspace, u_trg, n_trg, n_slices, params);
     hipError_t err = hipGetLastError();
@@ -736,6 +945,28 @@ hipError_t launch_stresslet_normal_density(const double *r_src, const double *nd
                                            hipStream_t stream) {
     StressletNormalDensity::Params p{-3.0 / (4.0 * M_PI), reg * reg, eps * eps};
     return launch_pair<StressletNormalDensity>(r_src, nd, r_trg, u_trg, n_src, n_trg, p, stream);
+}
+
+/* Velocity gradients: g_trg is (n_trg, 9), G[i][j] at 9*it + 3*i + j. */
+hipError_t launch_stokeslet_grad(const double *r_src, const double *f_src, const double *r_trg,
+                                 double *g_trg, long long n_src, long long n_trg, double scale,
+                                 double reg, double eps, hipStream_t stream) {
+    StokesletGrad::Params p{scale, reg * reg, eps * eps};
+    return launch_pair<StokesletGrad>(r_src, f_src, r_trg, g_trg, n_src, n_trg, p, stream);
+}
+
+hipError_t launch_stresslet_grad(const double *r_src, const double *f_src, const double *r_trg,
+                                 double *g_trg, long long n_src, long long n_trg, double scale,
+                                 hipStream_t stream) {
+    StressletGrad::Params p{-3.0 * scale};
+    return launch_pair<StressletGrad>(r_src, f_src, r_trg, g_trg, n_src, n_trg, p, stream);
+}
+
+hipError_t launch_rotlet_grad(const double *r_src, const double *density, const double *r_trg,
+                              double *g_trg, long long n_src, long long n_trg, double factor,
+                              double reg, double eps, hipStream_t stream) {
+    RotletGrad::Params p{factor, reg * reg, eps * eps};
+    return launch_pair<RotletGrad>(r_src, density, r_trg, g_trg, n_src, n_trg, p, stream);
 }
 
 /* ---- batched oseen_tensor_direct dense builder (kernels.cpp:146-195) ---

@@ -30,6 +30,12 @@ hipError_t launch_rotlet(const double *, const double *, const double *, double 
 hipError_t launch_stresslet_normal_density(const double *, const double *, const double *,
                                            double *, long long, long long, double, double,
                                            hipStream_t);
+hipError_t launch_stokeslet_grad(const double *, const double *, const double *, double *,
+                                 long long, long long, double, double, double, hipStream_t);
+hipError_t launch_stresslet_grad(const double *, const double *, const double *, double *,
+                                 long long, long long, double, hipStream_t);
+hipError_t launch_rotlet_grad(const double *, const double *, const double *, double *, long long,
+                              long long, double, double, double, hipStream_t);
 hipError_t launch_oseen_tensor_batched(const double *, double *, long long, long long, double,
                                        double, double, hipStream_t);
 hipError_t launch_stresslet_times_normal(const double *, const double *, double *, long long,
@@ -120,11 +126,12 @@ Context &ctx() {
         }                                                                                          \
     } while (0)
 
-/* Shared host-pointer round trip: upload, launch via `fn`, download, sync. */
+/* Shared host-pointer round trip: upload, launch via `fn`, download, sync.
+ * outdim doubles per target come back (3 velocity components, 9 of a gradient). */
 template <typename LaunchFn>
 int host_eval(const char *where, const double *r_src, const double *f_src, int srcdim,
               long long n_src, const double *r_trg, double *u_trg, long long n_trg,
-              LaunchFn &&fn) {
+              LaunchFn &&fn, int outdim = 3) {
     if (n_src < 0 || n_trg < 0) {
         g_last_error = std::string(where) + ": negative size";
         return -1;
@@ -139,7 +146,7 @@ int host_eval(const char *where, const double *r_src, const double *f_src, int s
     CHK(where, c.ensure(Context::R_SRC, (size_t)(n_src ? n_src : 1) * 3 * 8, (void **)&d_rs));
     CHK(where, c.ensure(Context::F_SRC, (size_t)(n_src ? n_src : 1) * srcdim * 8, (void **)&d_fs));
     CHK(where, c.ensure(Context::R_TRG, (size_t)n_trg * 3 * 8, (void **)&d_rt));
-    CHK(where, c.ensure(Context::U_TRG, (size_t)n_trg * 3 * 8, (void **)&d_u));
+    CHK(where, c.ensure(Context::U_TRG, (size_t)n_trg * outdim * 8, (void **)&d_u));
     if (n_src) {
         CHK(where, hipMemcpyAsync(d_rs, r_src, (size_t)n_src * 3 * 8, hipMemcpyHostToDevice,
                                   c.stream));
@@ -148,7 +155,8 @@ int host_eval(const char *where, const double *r_src, const double *f_src, int s
     }
     CHK(where, hipMemcpyAsync(d_rt, r_trg, (size_t)n_trg * 3 * 8, hipMemcpyHostToDevice, c.stream));
     CHK(where, fn(d_rs, d_fs, d_rt, d_u, c.stream));
-    CHK(where, hipMemcpyAsync(u_trg, d_u, (size_t)n_trg * 3 * 8, hipMemcpyDeviceToHost, c.stream));
+    CHK(where, hipMemcpyAsync(u_trg, d_u, (size_t)n_trg * outdim * 8, hipMemcpyDeviceToHost,
+                              c.stream));
     CHK(where, hipStreamSynchronize(c.stream));
     return 0;
 }
@@ -293,6 +301,98 @@ int skelly_rotlet_device(const double *d_r_src, const double *d_r_trg, const dou
     CHK("skelly_rotlet_device",
         skelly::launch_rotlet(d_r_src, d_density, d_r_trg, d_u_trg, n_src, n_trg, factor, reg,
                               epsilon_distance, (hipStream_t)stream));
+    return 0;
+}
+
+/* ---- velocity gradients: 9 doubles per target, G[i][j] at 9*it + 3*i + j ---- */
+
+int skelly_stokeslet_grad_host(const double *r_src, const double *f_src, long long n_src,
+                               const double *r_trg, double *g_trg, long long n_trg, double eta) {
+    return host_eval("skelly_stokeslet_grad_host", r_src, f_src, 3, n_src, r_trg, g_trg, n_trg,
+                     [&](const double *rs, const double *fs, const double *rt, double *g,
+                         hipStream_t s) {
+                         return skelly::launch_stokeslet_grad(rs, fs, rt, g, n_src, n_trg,
+                                                              kOneOver8Pi / eta, 0.0, 0.0, s);
+                     },
+                     9);
+}
+
+int skelly_stresslet_grad_host(const double *r_src, const double *f_src, long long n_src,
+                               const double *r_trg, double *g_trg, long long n_trg, double eta) {
+    return host_eval("skelly_stresslet_grad_host", r_src, f_src, 9, n_src, r_trg, g_trg, n_trg,
+                     [&](const double *rs, const double *fs, const double *rt, double *g,
+                         hipStream_t s) {
+                         return skelly::launch_stresslet_grad(rs, fs, rt, g, n_src, n_trg,
+                                                              kOneOver8Pi / eta, s);
+                     },
+                     9);
+}
+
+int skelly_oseen_contract_grad_host(const double *r_src, const double *r_trg,
+                                    const double *density, double *g_trg, long long n_src,
+                                    long long n_trg, double eta, double reg,
+                                    double epsilon_distance) {
+    const double factor = 1.0 / (8.0 * M_PI * eta);
+    return host_eval("skelly_oseen_contract_grad_host", r_src, density, 3, n_src, r_trg, g_trg,
+                     n_trg,
+                     [&](const double *rs, const double *ds, const double *rt, double *g,
+                         hipStream_t s) {
+                         return skelly::launch_stokeslet_grad(rs, ds, rt, g, n_src, n_trg, factor,
+                                                              reg, epsilon_distance, s);
+                     },
+                     9);
+}
+
+int skelly_rotlet_grad_host(const double *r_src, const double *r_trg, const double *density,
+                            double *g_trg, long long n_src, long long n_trg, double eta,
+                            double reg, double epsilon_distance) {
+    const double factor = 1.0 / (8.0 * M_PI * eta);
+    return host_eval("skelly_rotlet_grad_host", r_src, density, 3, n_src, r_trg, g_trg, n_trg,
+                     [&](const double *rs, const double *ds, const double *rt, double *g,
+                         hipStream_t s) {
+                         return skelly::launch_rotlet_grad(rs, ds, rt, g, n_src, n_trg, factor,
+                                                           reg, epsilon_distance, s);
+                     },
+                     9);
+}
+
+int skelly_stokeslet_grad_device(const double *d_r_src, const double *d_f_src, long long n_src,
+                                 const double *d_r_trg, double *d_g_trg, long long n_trg,
+                                 double eta, void *stream) {
+    CHK("skelly_stokeslet_grad_device",
+        skelly::launch_stokeslet_grad(d_r_src, d_f_src, d_r_trg, d_g_trg, n_src, n_trg,
+                                      kOneOver8Pi / eta, 0.0, 0.0, (hipStream_t)stream));
+    return 0;
+}
+
+int skelly_stresslet_grad_device(const double *d_r_src, const double *d_f_src, long long n_src,
+                                 const double *d_r_trg, double *d_g_trg, long long n_trg,
+                                 double eta, void *stream) {
+    CHK("skelly_stresslet_grad_device",
+        skelly::launch_stresslet_grad(d_r_src, d_f_src, d_r_trg, d_g_trg, n_src, n_trg,
+                                      kOneOver8Pi / eta, (hipStream_t)stream));
+    return 0;
+}
+
+int skelly_oseen_contract_grad_device(const double *d_r_src, const double *d_r_trg,
+                                      const double *d_density, double *d_g_trg, long long n_src,
+                                      long long n_trg, double eta, double reg,
+                                      double epsilon_distance, void *stream) {
+    const double factor = 1.0 / (8.0 * M_PI * eta);
+    CHK("skelly_oseen_contract_grad_device",
+        skelly::launch_stokeslet_grad(d_r_src, d_density, d_r_trg, d_g_trg, n_src, n_trg, factor,
+                                      reg, epsilon_distance, (hipStream_t)stream));
+    return 0;
+}
+
+int skelly_rotlet_grad_device(const double *d_r_src, const double *d_r_trg,
+                              const double *d_density, double *d_g_trg, long long n_src,
+                              long long n_trg, double eta, double reg, double epsilon_distance,
+                              void *stream) {
+    const double factor = 1.0 / (8.0 * M_PI * eta);
+    CHK("skelly_rotlet_grad_device",
+        skelly::launch_rotlet_grad(d_r_src, d_density, d_r_trg, d_g_trg, n_src, n_trg, factor,
+                                   reg, epsilon_distance, (hipStream_t)stream));
     return 0;
 }
 

@@ -102,6 +102,60 @@ def rotlet_gpu(r_src, r_trg, density, eta=1.0, reg=5e-3, epsilon_distance=1e-5):
     return u
 
 
+# Velocity gradients, host arrays: (n_trg, 3, 3) with G[t, i, j] = du_i/dx_j at
+# target t, from the analytic gradient kernels (one pass, no differencing).
+
+def stokeslet_grad(r_src, f_src, r_trg, eta):
+    """Gradient of the Stokeslet velocity (stokeslet_direct_gpu's field)."""
+    src = _rows(r_src, 3, "r_src")
+    f = _rows(f_src, 3, "f_src")
+    trg = _rows(r_trg, 3, "r_trg")
+    g = np.zeros((len(trg), 3, 3))
+    rc = _native.lib().skelly_stokeslet_grad_host(_ptr(src), _ptr(f), len(src), _ptr(trg),
+                                                  _ptr(g), len(trg), float(eta))
+    _native.check(rc, "stokeslet_grad")
+    return g
+
+
+def stresslet_grad(r_src, f_src, r_trg, eta):
+    """Gradient of the stresslet velocity (stresslet_direct_gpu's field)."""
+    src = _rows(r_src, 3, "r_src")
+    f = _rows(f_src, 9, "f_src")
+    trg = _rows(r_trg, 3, "r_trg")
+    g = np.zeros((len(trg), 3, 3))
+    rc = _native.lib().skelly_stresslet_grad_host(_ptr(src), _ptr(f), len(src), _ptr(trg),
+                                                  _ptr(g), len(trg), float(eta))
+    _native.check(rc, "stresslet_grad")
+    return g
+
+
+def oseen_contract_grad(r_src, r_trg, density, eta=1.0, reg=5e-3, epsilon_distance=1e-5):
+    """Gradient of oseen_contract_direct_gpu's field (exact inside each branch
+    of the regularization)."""
+    src = _rows(r_src, 3, "r_src")
+    trg = _rows(r_trg, 3, "r_trg")
+    rho = _rows(density, 3, "density")
+    g = np.zeros((len(trg), 3, 3))
+    rc = _native.lib().skelly_oseen_contract_grad_host(_ptr(src), _ptr(trg), _ptr(rho), _ptr(g),
+                                                       len(src), len(trg), float(eta),
+                                                       float(reg), float(epsilon_distance))
+    _native.check(rc, "oseen_contract_grad")
+    return g
+
+
+def rotlet_grad(r_src, r_trg, density, eta=1.0, reg=5e-3, epsilon_distance=1e-5):
+    """Gradient of rotlet_gpu's field."""
+    src = _rows(r_src, 3, "r_src")
+    trg = _rows(r_trg, 3, "r_trg")
+    rho = _rows(density, 3, "density")
+    g = np.zeros((len(trg), 3, 3))
+    rc = _native.lib().skelly_rotlet_grad_host(_ptr(src), _ptr(trg), _ptr(rho), _ptr(g),
+                                               len(src), len(trg), float(eta), float(reg),
+                                               float(epsilon_distance))
+    _native.check(rc, "rotlet_grad")
+    return g
+
+
 class Evaluator:
     """Callable mirroring kernels::Evaluator for one kernel type."""
 
@@ -278,4 +332,76 @@ def rotlet_device(r_src, r_trg, density, eta=1.0, reg=5e-3, epsilon_distance=1e-
         ctypes.c_void_p(density.data_ptr()), ctypes.c_void_p(out.data_ptr()),
         len(r_src), len(r_trg), float(eta), float(reg), float(epsilon_distance), _stream_ptr())
     _native.check(rc, "rotlet_device")
+    return out
+
+
+# ---------------------------------------------------------------------------
+# velocity gradients on device tensors: (n_trg, 3, 3), G[t, i, j] = du_i/dx_j
+# ---------------------------------------------------------------------------
+
+def _grad_out(r_trg, out):
+    import torch
+    if out is None:
+        return torch.empty((len(r_trg), 3, 3), dtype=torch.float64, device=r_trg.device)
+    if not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()
+            and out.numel() == 9 * len(r_trg)):
+        raise ValueError("out: expected a contiguous float64 CUDA tensor of (n_trg, 3, 3)")
+    return out
+
+
+def stokeslet_grad_device(r_src, f_src, r_trg, eta, out=None):
+    """Gradient of stokeslet_device's field. Async on torch's current stream."""
+    r_src = _dev_rows(r_src, 3, "r_src")
+    f_src = _dev_rows(f_src, 3, "f_src")
+    r_trg = _dev_rows(r_trg, 3, "r_trg")
+    out = _grad_out(r_trg, out)
+    rc = _native.lib().skelly_stokeslet_grad_device(
+        ctypes.c_void_p(r_src.data_ptr()), ctypes.c_void_p(f_src.data_ptr()), len(r_src),
+        ctypes.c_void_p(r_trg.data_ptr()), ctypes.c_void_p(out.data_ptr()), len(r_trg),
+        float(eta), _stream_ptr())
+    _native.check(rc, "stokeslet_grad_device")
+    return out
+
+
+def stresslet_grad_device(r_src, f_src, r_trg, eta, out=None):
+    """Gradient of stresslet_device's field."""
+    r_src = _dev_rows(r_src, 3, "r_src")
+    f_src = _dev_rows(f_src, 9, "f_src")
+    r_trg = _dev_rows(r_trg, 3, "r_trg")
+    out = _grad_out(r_trg, out)
+    rc = _native.lib().skelly_stresslet_grad_device(
+        ctypes.c_void_p(r_src.data_ptr()), ctypes.c_void_p(f_src.data_ptr()), len(r_src),
+        ctypes.c_void_p(r_trg.data_ptr()), ctypes.c_void_p(out.data_ptr()), len(r_trg),
+        float(eta), _stream_ptr())
+    _native.check(rc, "stresslet_grad_device")
+    return out
+
+
+def oseen_contract_grad_device(r_src, r_trg, density, eta=1.0, reg=5e-3,
+                               epsilon_distance=1e-5, out=None):
+    """Gradient of oseen_contract_device's field."""
+    r_src = _dev_rows(r_src, 3, "r_src")
+    r_trg = _dev_rows(r_trg, 3, "r_trg")
+    density = _dev_rows(density, 3, "density")
+    out = _grad_out(r_trg, out)
+    rc = _native.lib().skelly_oseen_contract_grad_device(
+        ctypes.c_void_p(r_src.data_ptr()), ctypes.c_void_p(r_trg.data_ptr()),
+        ctypes.c_void_p(density.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+        len(r_src), len(r_trg), float(eta), float(reg), float(epsilon_distance), _stream_ptr())
+    _native.check(rc, "oseen_contract_grad_device")
+    return out
+
+
+def rotlet_grad_device(r_src, r_trg, density, eta=1.0, reg=5e-3, epsilon_distance=1e-5,
+                       out=None):
+    """Gradient of rotlet_device's field."""
+    r_src = _dev_rows(r_src, 3, "r_src")
+    r_trg = _dev_rows(r_trg, 3, "r_trg")
+    density = _dev_rows(density, 3, "density")
+    out = _grad_out(r_trg, out)
+    rc = _native.lib().skelly_rotlet_grad_device(
+        ctypes.c_void_p(r_src.data_ptr()), ctypes.c_void_p(r_trg.data_ptr()),
+        ctypes.c_void_p(density.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+        len(r_src), len(r_trg), float(eta), float(reg), float(epsilon_distance), _stream_ptr())
+    _native.check(rc, "rotlet_grad_device")
     return out

@@ -19,13 +19,19 @@ Mirrors:
                         solution all-gathered per apply (the reference's
                         MPI_Allgatherv, periphery.cpp:26,44 -> RCCL).
 
+The `*_flow_grad` / velocity_gradient_at_targets forms return the analytic
+velocity gradient G[t, i, j] = du_i/dx_j of the same fields (no reference
+counterpart: the reference differences the velocity), with
+vorticity_from_gradient / strain_rate_from_gradient on top.
+
 All tensors are torch fp64; the pair-kernel legs require CUDA tensors (the
 product path; no CPU fallback).
 """
 
 import torch
 
-from .evaluator import stokeslet_device, stresslet_device
+from .evaluator import (stokeslet_device, stresslet_device, stokeslet_grad_device,
+                        stresslet_grad_device)
 from .sharded import allgather_rows
 
 
@@ -118,6 +124,75 @@ def velocity_at_targets(r_trg, eta, fiber=None, shell=None, bodies=None):
         u = u + body_flow(bodies["node_pos"], bodies["node_normals"], bodies["densities"],
                           bodies["centers"], bodies["forces"], bodies["torques"], r_trg, eta)
     return u
+
+
+def _zero_grad(r_trg):
+    return torch.zeros((r_trg.shape[0], 3, 3), dtype=r_trg.dtype, device=r_trg.device)
+
+
+def periphery_flow_grad(node_pos, node_normal, density, r_trg, eta):
+    """Velocity gradient (n_trg, 3, 3), G[t, i, j] = du_i/dx_j, of
+    periphery_flow's field: the same f_dl through the stresslet gradient
+    kernel."""
+    if node_pos.shape[0] == 0:
+        return _zero_grad(r_trg)
+    f_dl = 2.0 * eta * torch.einsum("ni,nj->nij", node_normal, density).reshape(-1, 9)
+    return stresslet_grad_device(node_pos, f_dl.contiguous(), r_trg, eta)
+
+
+def fiber_flow_grad(r_src, fib_forces, weights, r_trg, eta):
+    """Velocity gradient of fiber_flow's field without the self term (the
+    reference's subtract_self = false, the post-processing form)."""
+    if r_src.shape[0] == 0:
+        return _zero_grad(r_trg)
+    wf = fib_forces * weights[:, None]
+    return stokeslet_grad_device(r_src, wf.contiguous(), r_trg, eta)
+
+
+def body_flow_grad(node_pos, node_normals, densities, centers, forces, torques, r_trg, eta,
+                   reg=5e-3, epsilon_distance=1e-5):
+    """Velocity gradient of body_flow's field, term by term."""
+    g = periphery_flow_grad(node_pos, node_normals, densities, r_trg, eta)
+    if centers.shape[0]:
+        g = g + stokeslet_grad_device(centers, forces, r_trg, eta)
+        from .evaluator import rotlet_grad_device
+        g = g + rotlet_grad_device(centers, r_trg, torques, eta, reg, epsilon_distance)
+    return g
+
+
+def velocity_gradient_at_targets(r_trg, eta, fiber=None, shell=None, bodies=None):
+    """Gradient (n_trg, 3, 3) of velocity_at_targets' field, same dict
+    inputs; the fiber self term is never subtracted (fiber_flow_grad)."""
+    g = _zero_grad(r_trg)
+    if fiber is not None:
+        g = g + fiber_flow_grad(fiber["r_src"], fiber["forces"], fiber["weights"], r_trg, eta)
+    if shell is not None:
+        g = g + periphery_flow_grad(shell["node_pos"], shell["node_normal"], shell["density"],
+                                    r_trg, eta)
+    if bodies is not None:
+        g = g + body_flow_grad(bodies["node_pos"], bodies["node_normals"], bodies["densities"],
+                               bodies["centers"], bodies["forces"], bodies["torques"], r_trg,
+                               eta)
+    return g
+
+
+def vorticity_from_gradient(G):
+    """Curl of the velocity from G[..., i, j] = du_i/dx_j (torch or numpy):
+    (G21 - G12, G02 - G20, G10 - G01)."""
+    w = (G[..., 2, 1] - G[..., 1, 2], G[..., 0, 2] - G[..., 2, 0],
+         G[..., 1, 0] - G[..., 0, 1])
+    if torch.is_tensor(G):
+        return torch.stack(w, dim=-1)
+    import numpy as np
+    return np.stack(w, axis=-1)
+
+
+def strain_rate_from_gradient(G):
+    """Symmetric part of G: E = (G + G^T) / 2."""
+    if torch.is_tensor(G):
+        return 0.5 * (G + G.transpose(-1, -2))
+    import numpy as np
+    return 0.5 * (G + np.swapaxes(G, -1, -2))
 
 
 class ShellOperator:

@@ -22,7 +22,14 @@ Streamlines are integrated per the reference's adaptive
 5(4) RK scheme (see integrate_streamline); vortex lines are streamlines of
 the central-difference curl of the velocity field (streamline.cpp:16-35,
 115-165), with the singularity stop still on the VELOCITY norm
-(streamline.cpp:51, same observer for both line kinds)."""
+(streamline.cpp:51, same observer for both line kinds).
+
+Two extension keys, which the reference client never sends and without
+which every response is unchanged: `"analytic": true` in the `vortexlines`
+map integrates the analytic curl (velocity_gradient_field, one gradient
+evaluation per point instead of six velocity probes), and a
+`"velocity_gradient": {"x": ...}` entry adds a 9 x n `velocity_gradient`
+block (column t = row-major du_i/dx_j at target t) to the response."""
 
 import argparse
 import os
@@ -48,6 +55,12 @@ def eigen_decode(d):
     if isinstance(d, dict):
         return {k: eigen_decode(v) for k, v in d.items()}
     return d
+
+
+def eigen_encode_9xn(g):
+    """(n, 3, 3) -> ['__eigen__', 9, n, colmajor]: column t is G[t] row-major."""
+    g = np.asarray(g, dtype=np.float64).reshape(-1, 9)
+    return ["__eigen__", 9, len(g), *g.reshape(-1).tolist()]
 
 
 def eigen_encode_3xn(a):
@@ -125,6 +138,49 @@ def bodies_from_frame(frame, body_geometry):
     return bodies
 
 
+def _fiber_sources(fibers):
+    """Stokeslet sources of the fiber flow: node positions and the
+    quadrature-weighted forces force_operator @ [x | tension]."""
+    r_src, wf = [], []
+    for f in fibers:
+        sol = np.concatenate([f.x.reshape(-1), f.tension])
+        ff = f.force_operator @ sol  # apply_fiber_force, system.cpp:339
+        fn = np.stack([ff[i * f.n_nodes:(i + 1) * f.n_nodes]
+                       for i in range(3)], axis=1)
+        r_src.append(f.x.T)
+        wf.append(fn * f.quadrature_weights()[:, None])
+    return np.concatenate(r_src), np.concatenate(wf)
+
+
+def _shell_density(frame, shell_geometry):
+    """The frame's shell double-layer density (n, 3), or None when the shell
+    does not take part."""
+    if shell_geometry is None or "shell" not in frame:
+        return None
+    dens = np.asarray(frame["shell"].get("solution_vec_", np.zeros(0)),
+                      float).reshape(-1)
+    return dens.reshape(-1, 3) if dens.size else None
+
+
+def _body_sources(fibers, bodies):
+    """Sources of bc_.flow with the frame solution: the double layer and the
+    center stokeslet/rotlet strengths of the LINK forces (system.cpp:349-357;
+    external forces are zeroed there, per the reference's own comment).
+    Returns nodes, normals, densities, centers, ft (n_bodies, 6)."""
+    from .body import calculate_link_conditions
+    nodes = np.concatenate([b.nodes for b in bodies])
+    normals = np.concatenate([b.normals for b in bodies])
+    dens = np.concatenate([b.solution_vec[: 3 * b.n_nodes].reshape(-1, 3)
+                           for b in bodies])
+    body_vels = np.stack([np.concatenate([b.velocity, b.angular_velocity])
+                          for b in bodies])
+    x_fib = np.concatenate([np.concatenate([f.x.reshape(-1), f.tension])
+                            for f in fibers]) if fibers else np.zeros(0)
+    _, ft = calculate_link_conditions(fibers, x_fib, body_vels, bodies)
+    centers = np.stack([b.position for b in bodies])
+    return nodes, normals, dens, centers, ft
+
+
 def velocity_field(frame, targets, eta, compute, shell_geometry=None,
                    body_geometry=None, sources=None):
     """System::velocity_at_targets (system.cpp:330-384) for fibers
@@ -142,42 +198,19 @@ def velocity_field(frame, targets, eta, compute, shell_geometry=None,
             u += bs.flow(targets, eta)
     fibers = fibers_from_frame(frame, eta)
     if fibers:
-        r_src, wf = [], []
-        for f in fibers:
-            sol = np.concatenate([f.x.reshape(-1), f.tension])
-            ff = f.force_operator @ sol  # apply_fiber_force, system.cpp:339
-            fn = np.stack([ff[i * f.n_nodes:(i + 1) * f.n_nodes]
-                           for i in range(3)], axis=1)
-            r_src.append(f.x.T)
-            wf.append(fn * f.quadrature_weights()[:, None])
+        r_src, wf = _fiber_sources(fibers)
         # fc_->flow(..., subtract_self=false), system.cpp:355
-        u += compute.stokeslet(np.concatenate(r_src), np.concatenate(wf),
-                               targets, eta)
-    if shell_geometry is not None and "shell" in frame:
-        dens = np.asarray(frame["shell"].get("solution_vec_", np.zeros(0)),
-                          float).reshape(-1)
-        if dens.size:
-            u += compute.stresslet_normal_density(
-                shell_geometry["nodes"], shell_geometry["normals"],
-                dens.reshape(-1, 3), targets, eta)
+        u += compute.stokeslet(r_src, wf, targets, eta)
+    dens = _shell_density(frame, shell_geometry)
+    if dens is not None:
+        u += compute.stresslet_normal_density(
+            shell_geometry["nodes"], shell_geometry["normals"], dens,
+            targets, eta)
     bodies = bodies_from_frame(frame, body_geometry) \
         if body_geometry is not None else []
     if bodies:
-        from .body import calculate_link_conditions
-        # bc_.flow with the frame solution: double layer + center
-        # stokeslet/rotlet of the LINK forces (system.cpp:349-357; external
-        # forces are zeroed there, per the reference's own comment)
-        nodes = np.concatenate([b.nodes for b in bodies])
-        normals = np.concatenate([b.normals for b in bodies])
-        dens = np.concatenate([b.solution_vec[: 3 * b.n_nodes].reshape(-1, 3)
-                               for b in bodies])
+        nodes, normals, dens, centers, ft = _body_sources(fibers, bodies)
         u += compute.stresslet_normal_density(nodes, normals, dens, targets, eta)
-        body_vels = np.stack([np.concatenate([b.velocity, b.angular_velocity])
-                              for b in bodies])
-        x_fib = np.concatenate([np.concatenate([f.x.reshape(-1), f.tension])
-                                for f in fibers]) if fibers else np.zeros(0)
-        _, ft = calculate_link_conditions(fibers, x_fib, body_vels, bodies)
-        centers = np.stack([b.position for b in bodies])
         u += compute.stokeslet(centers, ft[:, 0:3], targets, eta)
         u += compute.rotlet(centers, ft[:, 3:6], targets, eta)
         # points inside a body move rigidly (system.cpp:363-371)
@@ -189,6 +222,47 @@ def velocity_field(frame, targets, eta, compute, shell_geometry=None,
                     np.cross(np.broadcast_to(b.angular_velocity, (int(inside.sum()), 3)),
                              dx[inside])
     return u
+
+
+def velocity_gradient_field(frame, targets, eta, compute, shell_geometry=None,
+                            body_geometry=None, sources=None):
+    """Analytic gradient (n, 3, 3), G[t, i, j] = du_i/dx_j, of velocity_field:
+    the same terms from the same sources, each through the backend's `_grad`
+    method. Inside a body the field is the rigid motion, so G is the rotation
+    matrix G_ij = eps_ikj omega_k there."""
+    targets = np.asarray(targets, float).reshape(-1, 3)
+    G = np.zeros((len(targets), 3, 3))
+    if sources is not None:
+        psc, bs = sources
+        if psc is not None:
+            G += psc.flow_grad(targets, eta, float(frame.get("time", 0.0)), compute)
+        if bs is not None and bs.is_active():
+            G += bs.flow_grad(targets)
+    fibers = fibers_from_frame(frame, eta)
+    if fibers:
+        r_src, wf = _fiber_sources(fibers)
+        G += compute.stokeslet_grad(r_src, wf, targets, eta)
+    dens = _shell_density(frame, shell_geometry)
+    if dens is not None:
+        G += compute.stresslet_normal_density_grad(
+            shell_geometry["nodes"], shell_geometry["normals"], dens,
+            targets, eta)
+    bodies = bodies_from_frame(frame, body_geometry) \
+        if body_geometry is not None else []
+    if bodies:
+        nodes, normals, dens, centers, ft = _body_sources(fibers, bodies)
+        G += compute.stresslet_normal_density_grad(nodes, normals, dens, targets, eta)
+        G += compute.stokeslet_grad(centers, ft[:, 0:3], targets, eta)
+        G += compute.rotlet_grad(centers, ft[:, 3:6], targets, eta)
+        for b in bodies:
+            dx = targets - b.position[None, :]
+            inside = np.linalg.norm(dx, axis=1) < b.radius
+            if inside.any():
+                w = b.angular_velocity
+                G[inside] = np.array([[0.0, -w[2], w[1]],
+                                      [w[2], 0.0, -w[0]],
+                                      [-w[1], w[0], 0.0]])
+    return G
 
 
 def vorticity(field_fn, pts, eps=1e-7):
@@ -260,7 +334,10 @@ def integrate_streamline(field_fn, x0, dt_init=0.1, t_final=1.0, abs_err=1e-10,
 def process_streamlines(frame, req, eta, compute, shell_geometry,
                         vortex=False, body_geometry=None, sources=None):
     """process_streamlines / process_vortexlines (listener.cpp:51-74): one
-    line per seed column; vortex=True integrates the curl field instead."""
+    line per seed column; vortex=True integrates the curl field instead —
+    the reference's central difference of the velocity, or, when the request
+    map carries "analytic": true (an extension), the curl of
+    velocity_gradient_field."""
     req = req or {}
     x0 = eigen_decode(req.get("x0", []))
     x0 = np.asarray(x0, float).reshape(-1, 3) if np.size(x0) else np.zeros((0, 3))
@@ -269,7 +346,13 @@ def process_streamlines(frame, req, eta, compute, shell_geometry,
     field = lambda pts: velocity_field(frame, pts, eta, compute,
                                        shell_geometry, body_geometry,
                                        sources)
-    rhs_fn = (lambda pts: vorticity(field, pts)) if vortex else None
+    rhs_fn = None
+    if vortex and req.get("analytic"):
+        from .flows import vorticity_from_gradient
+        rhs_fn = lambda pts: vorticity_from_gradient(velocity_gradient_field(
+            frame, pts, eta, compute, shell_geometry, body_geometry, sources))
+    elif vortex:
+        rhs_fn = lambda pts: vorticity(field, pts)
     out = []
     for seed in x0:
         s = integrate_streamline(field, seed,
@@ -329,6 +412,15 @@ def serve(stdin, stdout, traj, compute, eta=1.0, shell_geometry=None,
                                                sources=sources),
             "velocity_field": eigen_encode_3xn(u),
         }
+        vg = cmd.get("velocity_gradient")
+        if vg:
+            xg = eigen_decode(vg.get("x", []))
+            xg = np.asarray(xg, float).reshape(-1, 3) if np.size(xg) \
+                else np.zeros((0, 3))
+            response["velocity_gradient"] = eigen_encode_9xn(
+                velocity_gradient_field(frame, xg, eta, compute, shell_geometry,
+                                        body_geometry, sources)
+                if len(xg) else np.zeros((0, 3, 3)))
         out = msgpack.packb(response)
         stdout.write(struct.pack("<Q", len(out)))
         stdout.write(out)

@@ -54,6 +54,25 @@ class PointSourceContainer:
                 np.asarray(r_trg, float), eta)
         return vel
 
+    def flow_grad(self, r_trg, eta, time, backend):
+        """Velocity gradient (n_trg, 3, 3) of flow(): same liveness rules,
+        the backend's oseen_contract_grad / rotlet_grad."""
+        r_trg = np.asarray(r_trg, float)
+        grad = np.zeros((len(r_trg), 3, 3))
+        live = [p for p in self.points
+                if not (p.time_to_live and time >= p.time_to_live)]
+        forcers = [p for p in live if p.force.any()]
+        torquers = [p for p in live if p.torque.any()]
+        if forcers:
+            grad += backend.oseen_contract_grad(
+                np.stack([p.position for p in forcers]), r_trg,
+                np.stack([p.force for p in forcers]), eta)
+        if torquers:
+            grad += backend.rotlet_grad(
+                np.stack([p.position for p in torquers]),
+                np.stack([p.torque for p in torquers]), r_trg, eta)
+        return grad
+
 
 class BackgroundSource:
     """background_source.cpp:14-22: v_j(r) = uniform_j +
@@ -79,3 +98,10 @@ class BackgroundSource:
         r = np.asarray(r_trg, float)
         return self.uniform[None, :] + r[:, self.components] \
             * self.scale_factor[None, :]
+
+    def flow_grad(self, r_trg):
+        """Velocity gradient (n_trg, 3, 3) of flow(): the constant matrix
+        G[j, components[j]] = scale_factor[j]."""
+        G = np.zeros((3, 3))
+        G[np.arange(3), self.components] = self.scale_factor
+        return np.broadcast_to(G, (len(np.asarray(r_trg, float).reshape(-1, 3)), 3, 3)).copy()

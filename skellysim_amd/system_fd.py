@@ -78,6 +78,35 @@ class HipBackend:
         self.torch.cuda.synchronize()
         return u.cpu().numpy()
 
+    # velocity gradients: (n_trg, 3, 3), G[t, i, j] = du_i/dx_j
+
+    def stokeslet_grad(self, r_src, f_src, r_trg, eta):
+        from .evaluator import stokeslet_grad_device
+        g = stokeslet_grad_device(self._t(r_src), self._t(f_src), self._t(r_trg), eta)
+        self.torch.cuda.synchronize()
+        return g.cpu().numpy()
+
+    def stresslet_normal_density_grad(self, r_src, normals, density, r_trg, eta):
+        """Gradient of stresslet_normal_density's field (same f_dl)."""
+        from .evaluator import stresslet_grad_device
+        f_dl = 2.0 * eta * np.einsum("ni,nj->nij", normals, density).reshape(-1, 9)
+        g = stresslet_grad_device(self._t(r_src), self._t(f_dl), self._t(r_trg), eta)
+        self.torch.cuda.synchronize()
+        return g.cpu().numpy()
+
+    def rotlet_grad(self, centers, torques, r_trg, eta):
+        from .evaluator import rotlet_grad_device
+        g = rotlet_grad_device(self._t(centers), self._t(r_trg), self._t(torques), eta)
+        self.torch.cuda.synchronize()
+        return g.cpu().numpy()
+
+    def oseen_contract_grad(self, r_src, r_trg, density, eta):
+        from .evaluator import oseen_contract_grad_device
+        g = oseen_contract_grad_device(self._t(r_src), self._t(r_trg),
+                                       self._t(density), eta)
+        self.torch.cuda.synchronize()
+        return g.cpu().numpy()
+
     def stresslet_times_normal(self, nodes, normals, eta):
         """Dense (3n, 3n) operator (kernels.cpp:264-287; eta-independent
         factor) — the M block of the body preconditioner."""
