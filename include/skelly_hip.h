@@ -59,6 +59,14 @@ void skelly_set_persistent_ws(int on);
  * mode; the switch exists for A/B timing and for the tests that check that. */
 void skelly_set_pair_fastpath(int mode);
 
+/* Source-slice count of the pair kernels' split launches (overrides the env
+ * var SKELLY_PAIR_SLICES). 0 = chosen per launch by the CU load-balance
+ * planner (default); n >= 1 = exactly n slices, clamped only to the source
+ * count (and the grid limit 65535), for sweeps and tests. The slice count
+ * fixes the per-target summation order: results are bit-reproducible for a
+ * given count and agree to rounding between counts. */
+void skelly_set_pair_slices(int n);
+
 /* Human-readable build id ("skelly-hip <ver> gfx950"). */
 const char *skelly_hip_version(void);
 

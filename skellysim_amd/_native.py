@@ -63,6 +63,8 @@ def _bind(lib):
     lib.skelly_set_persistent_ws.restype = None
     lib.skelly_set_pair_fastpath.argtypes = [ctypes.c_int]
     lib.skelly_set_pair_fastpath.restype = None
+    lib.skelly_set_pair_slices.argtypes = [ctypes.c_int]
+    lib.skelly_set_pair_slices.restype = None
 
 
 def lib():
@@ -89,6 +91,14 @@ def set_pair_fastpath(mode):
     each walk >= 8192 sources), 2 always on. Results are bit-identical in
     every mode."""
     lib().skelly_set_pair_fastpath(int(mode))
+
+
+def set_pair_slices(n):
+    """Source-slice count of the pair kernels' split launches: 0 (default)
+    lets the launch planner choose, n >= 1 forces exactly n slices (clamped
+    to the source count). The count fixes the summation order, so results
+    are bit-identical for equal counts and equal to rounding otherwise."""
+    lib().skelly_set_pair_slices(int(n))
 
 
 def check(rc, what):

@@ -38,9 +38,17 @@
  *     see pair_fastpath_mode.
  *   - Accumulation order per target is source order (tile-major), fixed ->
  *     bit-reproducible for a given shard layout and slice count.
- *   - Small target counts (< 512 workgroups at one target/thread) switch to
- *     a source-split launch: gridDim.y source slices accumulate partials
+ *   - Source-split launches: gridDim.y source slices accumulate partials
  *     that a second kernel reduces in fixed slice order (deterministic).
+ *     The slice count comes from the launch planner of pair_plan.hpp: every
+ *     workgroup of a launch costs the same, so a CU's time goes with the
+ *     number of workgroups it gets, and the planner picks the count whose
+ *     blocks x slices workgroups divide most evenly over the CUs (the
+ *     flagship's 977 blocks: 6 slices, 22.9 -> 23 workgroups a CU, instead of
+ *     2 slices, 7.63 -> 8), with at least ~2048 sources a slice and the
+ *     partial workspace capped. A pure function of shape, CU count and
+ *     occupancy, so the summation order stays reproducible;
+ *     skelly_set_pair_slices() forces a count for sweeps and tests.
  *   - The same driver evaluates the analytic velocity gradients of the four
  *     kernels (9 outputs a target, K::OUTDIM; functors further down).
  *
@@ -55,6 +63,8 @@
 #include <map>
 #include <mutex>
 #include <vector>
+
+#include "pair_plan.hpp"
 
 #define BLOCK 256
 #define TILE 512
@@ -805,6 +815,70 @@ static int pair_fastpath_mode() {
     return mode;
 }
 
+/* Source-slice count of the split launches. 0 (default): the planner of
+ * pair_plan.hpp decides. n >= 1, from skelly_set_pair_slices() or else
+ * SKELLY_PAIR_SLICES: exactly n slices (clamped to n_src and to the
+ * gridDim.y limit), for sweeps and tests; slices may then be shorter than a
+ * tile, start anywhere, and the last ones may be empty (they write zeros). */
+static int g_pair_slices_override = -1; /* -1 = follow env var */
+
+static int pair_slices_forced() {
+    if (g_pair_slices_override >= 0)
+        return g_pair_slices_override;
+    static const int forced = [] {
+        const char *e = getenv("SKELLY_PAIR_SLICES");
+        const int v = e ? atoi(e) : 0;
+        return v < 0 ? 0 : v;
+    }();
+    return forced;
+}
+
+/* What the planner needs to know of the device, asked once per device and
+ * kernel: CU count and how many workgroups of the split instantiation a CU
+ * holds at once (stresslet 2, the others 3). A launch only reads the cached
+ * pair. */
+struct PairDeviceInfo {
+    int n_cu;
+    int wg_per_cu;
+};
+
+template <typename K, int TPT>
+static PairDeviceInfo pair_device_info() {
+    static std::mutex mu;
+    static std::map<int, PairDeviceInfo> cache;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find(dev);
+    if (it != cache.end())
+        return it->second;
+    /* defaults: MI355X; 256-thread blocks on 4 SIMDs, so waves/SIMD ==
+     * workgroups/CU */
+    PairDeviceInfo info{256, K::MIN_WAVES};
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+        info.n_cu = prop.multiProcessorCount;
+    int wg = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg, pair_driver<K, TPT, true>, BLOCK, 0) ==
+            hipSuccess &&
+        wg > 0)
+        info.wg_per_cu = wg;
+    (void)hipGetLastError();
+    cache[dev] = info;
+    return info;
+}
+
+template <typename K>
+static PairDeviceInfo pair_device_info_tpt(int tpt) {
+    if constexpr (K::MAX_TPT >= 4)
+        if (tpt == 4)
+            return pair_device_info<K, 4>();
+    if constexpr (K::MAX_TPT >= 2)
+        if (tpt == 2)
+            return pair_device_info<K, 2>();
+    return pair_device_info<K, 1>();
+}
+
 template <typename K>
 static inline int pick_tpt(long long n_trg) {
     /* Prefer 4 targets/thread (amortizes the per-source LDS broadcast reads
@@ -828,26 +902,15 @@ hipError_t launch_pair(const double *r_src, const double *f_src, const double *r
     const int tpt = pick_tpt<K>(n_trg);
     const long long blocks = (n_trg + (long long)BLOCK * tpt - 1) / ((long long)BLOCK * tpt);
 
-    /* Source-split when the target grid alone underfills the chip (256 CUs;
-     * aim >= SKELLY_SPLIT_TARGET workgroups, default 1024 — measured +11%
-     * over 512 at 1e5 x 1e5) and there are enough sources to slice. */
-    static const long long split_target = [] {
-        const char *e = getenv("SKELLY_SPLIT_TARGET");
-        long long v = e ? atoll(e) : 1024;
-        return v > 0 ? v : 1024;
-    }();
-    int n_slices = 1;
-    if (blocks < split_target) {
-        long long s = (split_target + blocks - 1) / blocks;
-        long long max_by_src = (n_src + 2047) / 2048; /* keep >= ~2048 src/slice */
-        n_slices = (int)(s < max_by_src ? s : max_by_src);
-        if (n_slices < 1)
-            n_slices = 1;
-    }
-
-    const int mode = pair_fastpath_mode();
-    const long long src_per_block = (n_src + n_slices - 1) / n_slices;
-    const int fast = mode == 2 || (mode == 1 && src_per_block >= PAIR_FASTPATH_MIN_SRC);
+    /* Source slices from the CU load-balance model (pair_plan.hpp): the
+     * slice count that leaves the CUs the least uneven numbers of
+     * workgroups, within the slice-length floor and the workspace cap. */
+    const PairDeviceInfo info = pair_device_info_tpt<K>(tpt);
+    const PairPlan plan =
+        pair_plan(n_src, n_trg, K::MAX_TPT, K::OUTDIM, pair_fastpath_mode(),
+                  PAIR_FASTPATH_MIN_SRC, info.n_cu, info.wg_per_cu, pair_slices_forced());
+    const int n_slices = plan.n_slices;
+    const int fast = plan.fast;
 
     dim3 block(BLOCK);
     if (n_slices == 1) {
@@ -1142,4 +1205,11 @@ extern "C" void skelly_set_persistent_ws(int on) {
  * (see pair_fastpath_mode above). Results do not depend on it. */
 extern "C" void skelly_set_pair_fastpath(int mode) {
     skelly::g_pair_fastpath_override = mode < 0 ? 0 : (mode > 2 ? 2 : mode);
+}
+
+/* Runtime override of the source-slice count: 0 = the planner, n >= 1 =
+ * exactly n slices (see pair_slices_forced above). Results depend on it only
+ * through the summation order. */
+extern "C" void skelly_set_pair_slices(int n) {
+    skelly::g_pair_slices_override = n < 0 ? 0 : n;
 }
