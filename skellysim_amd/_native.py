@@ -15,56 +15,57 @@ _LIB_PATH = os.path.join(_HERE, "libskellyhip.so")
 _lib = None
 _load_error = None
 
+_I = ctypes.c_int
+_D = ctypes.c_double
 _DP = ctypes.POINTER(ctypes.c_double)
 _LL = ctypes.c_longlong
+_PV = ctypes.c_void_p
+
+# The two argument orders of the pair entry points (include/skelly_hip.h); `p`
+# is the pointer type: double* in the host forms, void* in the device forms,
+# which end in one more void* for the stream.
+STRENGTH = "strength"  # (r_src, f_src, n_src, r_trg, out, n_trg, eta)
+DENSITY = "density"    # (r_src, r_trg, density, out, n_src, n_trg, eta, reg, eps)
+_PAIR_ARGS = {
+    STRENGTH: lambda p: [p, p, _LL, p, p, _LL, _D],
+    DENSITY: lambda p: [p, p, p, p, _LL, _LL, _D, _D, _D],
+}
+# skelly_<name>_host and skelly_<name>_device exist for every key
+PAIR_FAMILY = {
+    "stokeslet": STRENGTH, "stresslet": STRENGTH,
+    "stokeslet_grad": STRENGTH, "stresslet_grad": STRENGTH,
+    "oseen_contract": DENSITY, "rotlet": DENSITY,
+    "oseen_contract_grad": DENSITY, "rotlet_grad": DENSITY,
+}
+
+# every function of include/skelly_hip.h: name -> (restype, argtypes)
+SIGNATURES = {
+    "skelly_set_persistent_ws": (None, [_I]),
+    "skelly_set_pair_fastpath": (None, [_I]),
+    "skelly_set_pair_slices": (None, [_I]),
+    "skelly_hip_version": (ctypes.c_char_p, []),
+    "skelly_hip_last_error": (ctypes.c_char_p, []),
+    "skelly_hip_device_count": (_I, []),
+    "skelly_hip_set_device": (_I, [_I]),
+    "skelly_hip_shutdown": (_I, []),
+    "stokeslet_direct_gpu_impl": (None, [_DP, _DP, _I, _DP, _DP, _I]),
+    "stresslet_direct_gpu_impl": (None, [_DP, _DP, _I, _DP, _DP, _I]),
+    "skelly_stresslet_normal_density_host": (_I, [_DP, _DP, _DP, _DP, _LL, _D, _D]),
+    "skelly_stresslet_normal_density_device": (_I, [_PV, _PV, _PV, _PV, _LL, _LL, _D, _D, _PV]),
+    "skelly_stresslet_times_normal_device": (_I, [_PV, _PV, _PV, _LL, _D, _D, _PV]),
+    "skelly_oseen_tensor_batched_device": (_I, [_PV, _PV, _LL, _LL, _D, _D, _D, _PV]),
+    "skelly_fp64_peak_tflops": (_I, [_DP]),
+}
+for _name, _family in PAIR_FAMILY.items():
+    SIGNATURES[f"skelly_{_name}_host"] = (_I, _PAIR_ARGS[_family](_DP))
+    SIGNATURES[f"skelly_{_name}_device"] = (_I, _PAIR_ARGS[_family](_PV) + [_PV])
 
 
 def _bind(lib):
-    lib.skelly_hip_version.restype = ctypes.c_char_p
-    lib.skelly_hip_last_error.restype = ctypes.c_char_p
-    lib.skelly_hip_device_count.restype = ctypes.c_int
-    lib.skelly_hip_set_device.argtypes = [ctypes.c_int]
-    lib.stokeslet_direct_gpu_impl.argtypes = [_DP, _DP, ctypes.c_int, _DP, _DP, ctypes.c_int]
-    lib.stokeslet_direct_gpu_impl.restype = None
-    lib.stresslet_direct_gpu_impl.argtypes = [_DP, _DP, ctypes.c_int, _DP, _DP, ctypes.c_int]
-    lib.stresslet_direct_gpu_impl.restype = None
-    lib.skelly_stokeslet_host.argtypes = [_DP, _DP, _LL, _DP, _DP, _LL, ctypes.c_double]
-    lib.skelly_stresslet_host.argtypes = [_DP, _DP, _LL, _DP, _DP, _LL, ctypes.c_double]
-    lib.skelly_oseen_contract_host.argtypes = [_DP, _DP, _DP, _DP, _LL, _LL,
-                                               ctypes.c_double, ctypes.c_double, ctypes.c_double]
-    lib.skelly_rotlet_host.argtypes = [_DP, _DP, _DP, _DP, _LL, _LL,
-                                       ctypes.c_double, ctypes.c_double, ctypes.c_double]
-    pv = ctypes.c_void_p
-    lib.skelly_stokeslet_device.argtypes = [pv, pv, _LL, pv, pv, _LL, ctypes.c_double, pv]
-    lib.skelly_stresslet_device.argtypes = [pv, pv, _LL, pv, pv, _LL, ctypes.c_double, pv]
-    lib.skelly_oseen_contract_device.argtypes = [pv, pv, pv, pv, _LL, _LL,
-                                                 ctypes.c_double, ctypes.c_double,
-                                                 ctypes.c_double, pv]
-    lib.skelly_rotlet_device.argtypes = [pv, pv, pv, pv, _LL, _LL,
-                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, pv]
-    lib.skelly_stokeslet_grad_host.argtypes = lib.skelly_stokeslet_host.argtypes
-    lib.skelly_stresslet_grad_host.argtypes = lib.skelly_stresslet_host.argtypes
-    lib.skelly_oseen_contract_grad_host.argtypes = lib.skelly_oseen_contract_host.argtypes
-    lib.skelly_rotlet_grad_host.argtypes = lib.skelly_rotlet_host.argtypes
-    lib.skelly_stokeslet_grad_device.argtypes = lib.skelly_stokeslet_device.argtypes
-    lib.skelly_stresslet_grad_device.argtypes = lib.skelly_stresslet_device.argtypes
-    lib.skelly_oseen_contract_grad_device.argtypes = lib.skelly_oseen_contract_device.argtypes
-    lib.skelly_rotlet_grad_device.argtypes = lib.skelly_rotlet_device.argtypes
-    lib.skelly_stresslet_normal_density_host.argtypes = [_DP, _DP, _DP, _DP, _LL,
-                                                          ctypes.c_double, ctypes.c_double]
-    lib.skelly_stresslet_normal_density_device.argtypes = [pv, pv, pv, pv, _LL, _LL,
-                                                            ctypes.c_double, ctypes.c_double, pv]
-    lib.skelly_stresslet_times_normal_device.argtypes = [pv, pv, pv, _LL, ctypes.c_double,
-                                                          ctypes.c_double, pv]
-    lib.skelly_oseen_tensor_batched_device.argtypes = [pv, pv, _LL, _LL, ctypes.c_double,
-                                                        ctypes.c_double, ctypes.c_double, pv]
-    lib.skelly_fp64_peak_tflops.argtypes = [ctypes.POINTER(ctypes.c_double)]
-    lib.skelly_set_persistent_ws.argtypes = [ctypes.c_int]
-    lib.skelly_set_persistent_ws.restype = None
-    lib.skelly_set_pair_fastpath.argtypes = [ctypes.c_int]
-    lib.skelly_set_pair_fastpath.restype = None
-    lib.skelly_set_pair_slices.argtypes = [ctypes.c_int]
-    lib.skelly_set_pair_slices.restype = None
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = restype
+        fn.argtypes = argtypes
 
 
 def lib():

@@ -35,7 +35,7 @@
  *     tracks min(high dword of r^2) per chunk instead (one b32 op a pair).
  *     skelly_set_pair_fastpath(0) runs the masked path everywhere; by
  *     default small launches (under 128 chunks a block) stay masked too,
- *     see pair_fastpath_mode.
+ *     see g_pair_fastpath.
  *   - Accumulation order per target is source order (tile-major), fixed ->
  *     bit-reproducible for a given shard layout and slice count.
  *   - Source-split launches: gridDim.y source slices accumulate partials
@@ -62,8 +62,10 @@
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
+#include "pair_kernels.hpp"
 #include "pair_plan.hpp"
 
 #define BLOCK 256
@@ -114,7 +116,8 @@ __device__ inline double rsq_refined(double x) { return 0.5 * rsq_x2(x); }
 /* ---- kernel functors -------------------------------------------------
  * pair<MASKED>() adds one source's contribution to one target's
  * accumulators. With R = 2/r the accumulators hold ACC_FOLD times the plain
- * sum; the launch helpers divide Params::scale by ACC_FOLD.
+ * sum; the launch helpers divide Params::scale by ACC_FOLD. make_params()
+ * (host) builds Params from the C entry point's (scale, reg, eps).
  *   HAS_MASK   the kernel zeroes coincident pairs; MASKED=false leaves the
  *              select out and must make a coincident pair detectable.
  *   NAN_PROBE  an unmasked coincident pair turns the accumulators NaN
@@ -143,6 +146,7 @@ struct Stokeslet : VelocityTraits {
     struct Params {
         double scale; /* 1/(8*pi) [ / eta when folded] / ACC_FOLD */
     };
+    static Params make_params(double scale, double, double) { return {scale}; }
     /* u += (1/r)(f + rhat (f.rhat)); r = t - s; r==0 -> 0 (kernels.cu:62-76).
      * With R = 2/r and g = f/4: (g.d) R^2 = (f.d)/r^2, so each term is
      * R (f + d (f.d)/r^2) = 2x the plain one. */
@@ -181,6 +185,7 @@ struct Stresslet : VelocityTraits {
     struct Params {
         double scale; /* 1/(8*pi) [ / eta when folded] / ACC_FOLD */
     };
+    static Params make_params(double scale, double, double) { return {scale}; }
     /* u += -3 (d^T S d)/r^5 d; d = t - s; r==0 -> 0 (kernels.cu:29-54) */
     template <bool MASKED>
     __device__ static inline void pair(const double t[3], const double sp[3], const double f[9],
@@ -225,6 +230,9 @@ struct OseenContract : VelocityTraits {
         double reg2;
         double eps2;
     };
+    static Params make_params(double scale, double reg, double eps) {
+        return {scale, reg * reg, eps * eps};
+    }
     /* kernels.cpp:96-127: dr==0 skipped; dr > eps -> fr=1/dr, gr=1/dr^3;
      * else fr=1/sqrt(dr^2+reg^2), gr that cubed. The dr > eps comparison is
      * evaluated as dr2 > eps^2 (monotone equivalent for exact values; can
@@ -280,6 +288,9 @@ struct Rotlet : VelocityTraits {
         double reg2;
         double eps2;
     };
+    static Params make_params(double scale, double reg, double eps) {
+        return {scale, reg * reg, eps * eps};
+    }
     /* kernels.cpp:218-236: dr = dr2 < eps^2 ? sqrt(reg2+dr2) : sqrt(dr2)
      * (no dr==0 skip); fr = 1/dr^3; u += fr * (d x' rho) with the reference's
      * sign convention u_x += fr*(dz*rho_y - dy*rho_z), d = trg - src. */
@@ -321,6 +332,10 @@ struct StressletNormalDensity : VelocityTraits {
         double reg2;
         double eps2;
     };
+    /* the prefactor is the kernel's own: the caller's scale is not read */
+    static Params make_params(double, double reg, double eps) {
+        return {-3.0 / (4.0 * M_PI), reg * reg, eps * eps};
+    }
     /* kernels::stresslet_times_normal_times_density (kernels.cpp:307-334):
      * Sdn_i += (d.rho_j)(d.n_j)/r^5 d, d = trg - src; r_norm < eps ->
      * sqrt(r^2+reg^2) (kernels.cpp:320-323). The reference's i==j skip is a
@@ -397,6 +412,9 @@ struct StokesletGrad : GradTraits {
         double reg2;
         double eps2;
     };
+    static Params make_params(double scale, double reg, double eps) {
+        return {scale, reg * reg, eps * eps};
+    }
     template <bool MASKED>
     __device__ static inline void pair(const double t[3], const double sp[3], const double f[3],
                                        const double *, double acc[9], const Params &p,
@@ -449,6 +467,7 @@ struct StressletGrad : GradTraits {
     struct Params {
         double scale; /* -3/(8*pi*eta) / ACC_FOLD */
     };
+    static Params make_params(double scale, double, double) { return {-3.0 * scale}; }
     template <bool MASKED>
     __device__ static inline void pair(const double t[3], const double sp[3], const double f[9],
                                        const double *, double acc[9], const Params &,
@@ -505,6 +524,9 @@ struct RotletGrad : GradTraits {
         double reg2;
         double eps2;
     };
+    static Params make_params(double scale, double reg, double eps) {
+        return {scale, reg * reg, eps * eps};
+    }
     template <bool MASKED>
     __device__ static inline void pair(const double t[3], const double sp[3], const double rho[3],
                                        const double *, double acc[9], const Params &p,
@@ -742,6 +764,30 @@ __global__ __launch_bounds__(BLOCK) void reduce_partials(const double *__restric
 
 namespace skelly {
 
+namespace {
+/* A launch knob: the value a skelly_set_*() call forced (>= 0), else the
+ * environment variable, read once and passed through `clamp` (`dflt` without
+ * the variable). */
+struct Knob {
+    const char *env;
+    int dflt;
+    int (*clamp)(int);
+    int forced = -1; /* -1 = follow env var */
+    std::once_flag once;
+    int from_env = 0;
+
+    int get() {
+        if (forced >= 0)
+            return forced;
+        std::call_once(once, [this] {
+            const char *e = getenv(env);
+            from_env = clamp(e ? atoi(e) : dflt);
+        });
+        return from_env;
+    }
+};
+} // namespace
+
 /* Optional persistent split-K workspace (SKELLY_PERSISTENT_WS=1): replaces
  * the per-launch hipMallocAsync/hipFreeAsync pair with a grow-only buffer
  * cached per stream. Reuse across launches is safe because launches on one
@@ -752,17 +798,7 @@ namespace skelly {
  * alloc/free pairs are the prime suspect for the sync-cadence corruption
  * documented in gmres.py / DESIGN.md — flip this on to test that
  * hypothesis. */
-static int g_persistent_ws_override = -1; /* -1 = follow env var */
-
-static bool persistent_ws_enabled() {
-    if (g_persistent_ws_override >= 0)
-        return g_persistent_ws_override != 0;
-    static const bool on = [] {
-        const char *e = getenv("SKELLY_PERSISTENT_WS");
-        return e && atoi(e) != 0;
-    }();
-    return on;
-}
+static Knob g_persistent_ws{"SKELLY_PERSISTENT_WS", 0, [](int v) { return v != 0 ? 1 : 0; }};
 
 static double *persistent_ws(hipStream_t stream, size_t bytes) {
     struct Entry {
@@ -801,37 +837,16 @@ static double *persistent_ws(hipStream_t stream, size_t bytes) {
  * 24% / 17% SLOWER than the masked path, at 1e5 (9091 a slice) 7% faster
  * (profiles/pair_fastpath.md). 128 chunks bound the worst-case rerun at
  * 8/128 = 6% of the slice, under the ~8% the fast path gains. */
-static int g_pair_fastpath_override = -1; /* -1 = follow env var */
 static constexpr long long PAIR_FASTPATH_MIN_SRC = 128LL * SKELLY_CHUNK;
-
-static int pair_fastpath_mode() {
-    if (g_pair_fastpath_override >= 0)
-        return g_pair_fastpath_override;
-    static const int mode = [] {
-        const char *e = getenv("SKELLY_PAIR_FASTPATH");
-        const int v = e ? atoi(e) : 1;
-        return v < 0 ? 0 : (v > 2 ? 2 : v);
-    }();
-    return mode;
-}
+static Knob g_pair_fastpath{"SKELLY_PAIR_FASTPATH", 1,
+                            [](int v) { return v < 0 ? 0 : (v > 2 ? 2 : v); }};
 
 /* Source-slice count of the split launches. 0 (default): the planner of
  * pair_plan.hpp decides. n >= 1, from skelly_set_pair_slices() or else
  * SKELLY_PAIR_SLICES: exactly n slices (clamped to n_src and to the
  * gridDim.y limit), for sweeps and tests; slices may then be shorter than a
  * tile, start anywhere, and the last ones may be empty (they write zeros). */
-static int g_pair_slices_override = -1; /* -1 = follow env var */
-
-static int pair_slices_forced() {
-    if (g_pair_slices_override >= 0)
-        return g_pair_slices_override;
-    static const int forced = [] {
-        const char *e = getenv("SKELLY_PAIR_SLICES");
-        const int v = e ? atoi(e) : 0;
-        return v < 0 ? 0 : v;
-    }();
-    return forced;
-}
+static Knob g_pair_slices{"SKELLY_PAIR_SLICES", 0, [](int v) { return v < 0 ? 0 : v; }};
 
 /* What the planner needs to know of the device, asked once per device and
  * kernel: CU count and how many workgroups of the split instantiation a CU
@@ -868,15 +883,17 @@ static PairDeviceInfo pair_device_info() {
     return info;
 }
 
-template <typename K>
-static PairDeviceInfo pair_device_info_tpt(int tpt) {
+/* f(std::integral_constant<int, TPT>) for the runtime tpt, instantiating only
+ * what the functor's registers allow (K::MAX_TPT). */
+template <typename K, typename F>
+static auto dispatch_tpt(int tpt, F &&f) {
     if constexpr (K::MAX_TPT >= 4)
         if (tpt == 4)
-            return pair_device_info<K, 4>();
+            return f(std::integral_constant<int, 4>{});
     if constexpr (K::MAX_TPT >= 2)
         if (tpt == 2)
-            return pair_device_info<K, 2>();
-    return pair_device_info<K, 1>();
+            return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 1>{});
 }
 
 template <typename K>
@@ -892,9 +909,9 @@ static inline int pick_tpt(long long n_trg) {
 }
 
 template <typename K>
-hipError_t launch_pair(const double *r_src, const double *f_src, const double *r_trg,
-                       double *u_trg, long long n_src, long long n_trg,
-                       typename K::Params params, hipStream_t stream) {
+static hipError_t launch_pair(const double *r_src, const double *f_src, const double *r_trg,
+                              double *u_trg, long long n_src, long long n_trg,
+                              typename K::Params params, hipStream_t stream) {
     if (n_trg <= 0)
         return hipSuccess;
     /* the kernels accumulate ACC_FOLD x the sum (power of two: exact) */
@@ -905,32 +922,25 @@ hipError_t launch_pair(const double *r_src, const double *f_src, const double *r
     /* Source slices from the CU load-balance model (pair_plan.hpp): the
      * slice count that leaves the CUs the least uneven numbers of
      * workgroups, within the slice-length floor and the workspace cap. */
-    const PairDeviceInfo info = pair_device_info_tpt<K>(tpt);
+    const PairDeviceInfo info = dispatch_tpt<K>(
+        tpt, [](auto t) { return pair_device_info<K, decltype(t)::value>(); });
     const PairPlan plan =
-        pair_plan(n_src, n_trg, K::MAX_TPT, K::OUTDIM, pair_fastpath_mode(),
-                  PAIR_FASTPATH_MIN_SRC, info.n_cu, info.wg_per_cu, pair_slices_forced());
+        pair_plan(n_src, n_trg, K::MAX_TPT, K::OUTDIM, g_pair_fastpath.get(),
+                  PAIR_FASTPATH_MIN_SRC, info.n_cu, info.wg_per_cu, g_pair_slices.get());
     const int n_slices = plan.n_slices;
     const int fast = plan.fast;
 
     dim3 block(BLOCK);
+    /* pair_driver<K, tpt, PARTIAL> over `grid` into `dst` */
+    auto launch_driver = [&](auto partial, dim3 grid, double *dst) {
+        dispatch_tpt<K>(tpt, [&](auto t) {
+            hipLaunchKernelGGL((pair_driver<K, decltype(t)::value, decltype(partial)::value>),
+                               grid, block, 0, stream, r_src, f_src, r_trg, dst, n_src, n_trg,
+                               params, fast);
+        });
+    };
     if (n_slices == 1) {
-        dim3 grid((unsigned)blocks);
-        switch (tpt) {
-        case 4:
-            if constexpr (K::MAX_TPT >= 4)
-                hipLaunchKernelGGL((pair_driver<K, 4>), grid, block, 0, stream, r_src, f_src,
-                                   r_trg, u_trg, n_src, n_trg, params, fast);
-            break;
-        case 2:
-            if constexpr (K::MAX_TPT >= 2)
-                hipLaunchKernelGGL((pair_driver<K, 2>), grid, block, 0, stream, r_src, f_src,
-                                   r_trg, u_trg, n_src, n_trg, params, fast);
-            break;
-        default:
-            hipLaunchKernelGGL((pair_driver<K, 1>), grid, block, 0, stream, r_src, f_src,
-                               r_trg, u_trg, n_src, n_trg, params, fast);
-            break;
-        }
+        launch_driver(std::false_type{}, dim3((unsigned)blocks), u_trg);
         return hipGetLastError();
     }
 
@@ -938,7 +948,7 @@ hipError_t launch_pair(const double *r_src, const double *f_src, const double *r
     double *workspace = nullptr;
     bool pooled = false;
     const size_t ws_bytes = (size_t)n_slices * K::OUTDIM * n_trg * sizeof(double);
-    if (persistent_ws_enabled()) {
+    if (g_persistent_ws.get() != 0) {
         workspace = persistent_ws(stream, ws_bytes);
         pooled = workspace != nullptr;
     }
@@ -947,23 +957,7 @@ hipError_t launch_pair(const double *r_src, const double *f_src, const double *r
         if (err != hipSuccess)
             return err;
     }
-    dim3 grid((unsigned)blocks, (unsigned)n_slices);
-    switch (tpt) {
-    case 4:
-        if constexpr (K::MAX_TPT >= 4)
-            hipLaunchKernelGGL((pair_driver<K, 4, true>), grid, block, 0, stream, r_src, f_src,
-                               r_trg, workspace, n_src, n_trg, params, fast);
-        break;
-    case 2:
-        if constexpr (K::MAX_TPT >= 2)
-            hipLaunchKernelGGL((pair_driver<K, 2, true>), grid, block, 0, stream, r_src, f_src,
-                               r_trg, workspace, n_src, n_trg, params, fast);
-        break;
-    default:
-        hipLaunchKernelGGL((pair_driver<K, 1, true>), grid, block, 0, stream, r_src, f_src,
-                           r_trg, workspace, n_src, n_trg, params, fast);
-        break;
-    }
+    launch_driver(std::true_type{}, dim3((unsigned)blocks, (unsigned)n_slices), workspace);
     const long long rblocks = (K::OUTDIM * n_trg + BLOCK - 1) / BLOCK;
     hipLaunchKernelGGL((reduce_partials<K>), dim3((unsigned)rblocks), block, 0, stream,
                        workspace, u_trg, n_trg, n_slices, params);
@@ -974,62 +968,45 @@ hipError_t launch_pair(const double *r_src, const double *f_src, const double *r
     return err != hipSuccess ? err : err2;
 }
 
-hipError_t launch_stokeslet(const double *r_src, const double *f_src, const double *r_trg,
-                            double *u_trg, long long n_src, long long n_trg, double scale,
-                            hipStream_t stream) {
-    Stokeslet::Params p{scale};
-    return launch_pair<Stokeslet>(r_src, f_src, r_trg, u_trg, n_src, n_trg, p, stream);
+/* f(K{}) for the functor the enum names. */
+template <typename F>
+static auto with_kernel(PairKernel kernel, F &&f) {
+    switch (kernel) {
+    case PairKernel::Stokeslet:
+        return f(Stokeslet{});
+    case PairKernel::Stresslet:
+        return f(Stresslet{});
+    case PairKernel::OseenContract:
+        return f(OseenContract{});
+    case PairKernel::Rotlet:
+        return f(Rotlet{});
+    case PairKernel::StressletNormalDensity:
+        return f(StressletNormalDensity{});
+    case PairKernel::StokesletGrad:
+        return f(StokesletGrad{});
+    case PairKernel::StressletGrad:
+        return f(StressletGrad{});
+    case PairKernel::RotletGrad:
+        return f(RotletGrad{});
+    }
+    __builtin_unreachable();
 }
 
-hipError_t launch_stresslet(const double *r_src, const double *f_src, const double *r_trg,
-                            double *u_trg, long long n_src, long long n_trg, double scale,
-                            hipStream_t stream) {
-    Stresslet::Params p{scale};
-    return launch_pair<Stresslet>(r_src, f_src, r_trg, u_trg, n_src, n_trg, p, stream);
+PairDims pair_kernel_dims(PairKernel kernel) {
+    return with_kernel(kernel, [](auto k) {
+        using K = decltype(k);
+        return PairDims{K::SRCDIM, K::OUTDIM};
+    });
 }
 
-hipError_t launch_oseen(const double *r_src, const double *density, const double *r_trg,
-                        double *u_trg, long long n_src, long long n_trg, double factor,
-                        double reg, double eps, hipStream_t stream) {
-    OseenContract::Params p{factor, reg * reg, eps * eps};
-    return launch_pair<OseenContract>(r_src, density, r_trg, u_trg, n_src, n_trg, p, stream);
-}
-
-hipError_t launch_rotlet(const double *r_src, const double *density, const double *r_trg,
-                         double *u_trg, long long n_src, long long n_trg, double factor,
-                         double reg, double eps, hipStream_t stream) {
-    Rotlet::Params p{factor, reg * reg, eps * eps};
-    return launch_pair<Rotlet>(r_src, density, r_trg, u_trg, n_src, n_trg, p, stream);
-}
-
-hipError_t launch_stresslet_normal_density(const double *r_src, const double *nd,
-                                           const double *r_trg, double *u_trg, long long n_src,
-                                           long long n_trg, double reg, double eps,
-                                           hipStream_t stream) {
-    StressletNormalDensity::Params p{-3.0 / (4.0 * M_PI), reg * reg, eps * eps};
-    return launch_pair<StressletNormalDensity>(r_src, nd, r_trg, u_trg, n_src, n_trg, p, stream);
-}
-
-/* Velocity gradients: g_trg is (n_trg, 9), G[i][j] at 9*it + 3*i + j. */
-hipError_t launch_stokeslet_grad(const double *r_src, const double *f_src, const double *r_trg,
-                                 double *g_trg, long long n_src, long long n_trg, double scale,
-                                 double reg, double eps, hipStream_t stream) {
-    StokesletGrad::Params p{scale, reg * reg, eps * eps};
-    return launch_pair<StokesletGrad>(r_src, f_src, r_trg, g_trg, n_src, n_trg, p, stream);
-}
-
-hipError_t launch_stresslet_grad(const double *r_src, const double *f_src, const double *r_trg,
-                                 double *g_trg, long long n_src, long long n_trg, double scale,
-                                 hipStream_t stream) {
-    StressletGrad::Params p{-3.0 * scale};
-    return launch_pair<StressletGrad>(r_src, f_src, r_trg, g_trg, n_src, n_trg, p, stream);
-}
-
-hipError_t launch_rotlet_grad(const double *r_src, const double *density, const double *r_trg,
-                              double *g_trg, long long n_src, long long n_trg, double factor,
-                              double reg, double eps, hipStream_t stream) {
-    RotletGrad::Params p{factor, reg * reg, eps * eps};
-    return launch_pair<RotletGrad>(r_src, density, r_trg, g_trg, n_src, n_trg, p, stream);
+hipError_t launch_pair_kernel(PairKernel kernel, const double *r_src, const double *f_src,
+                              const double *r_trg, double *out, long long n_src, long long n_trg,
+                              double scale, double reg, double eps, hipStream_t stream) {
+    return with_kernel(kernel, [&](auto k) {
+        using K = decltype(k);
+        return launch_pair<K>(r_src, f_src, r_trg, out, n_src, n_trg,
+                              K::make_params(scale, reg, eps), stream);
+    });
 }
 
 /* ---- batched oseen_tensor_direct dense builder (kernels.cpp:146-195) ---
@@ -1193,23 +1170,23 @@ hipError_t run_fp64_peak(double *out_tflops) {
 } // namespace skelly
 
 /* Runtime override of the persistent split-K workspace (see
- * persistent_ws_enabled above): hipGraph capture of the GMRES iteration
+ * g_persistent_ws above): hipGraph capture of the GMRES iteration
  * (gmres.py use_graph) requires it — hipMallocAsync nodes cannot be
  * recorded reliably, and the grow-only hipMalloc happens during the
  * UNCAPTURED warmup pass, so capture itself allocates nothing. */
 extern "C" void skelly_set_persistent_ws(int on) {
-    skelly::g_persistent_ws_override = on;
+    skelly::g_persistent_ws.forced = on;
 }
 
 /* Runtime override of the unmasked pair fast path: 0 off, 1 auto, 2 always
- * (see pair_fastpath_mode above). Results do not depend on it. */
+ * (see g_pair_fastpath above). Results do not depend on it. */
 extern "C" void skelly_set_pair_fastpath(int mode) {
-    skelly::g_pair_fastpath_override = mode < 0 ? 0 : (mode > 2 ? 2 : mode);
+    skelly::g_pair_fastpath.forced = skelly::g_pair_fastpath.clamp(mode);
 }
 
 /* Runtime override of the source-slice count: 0 = the planner, n >= 1 =
- * exactly n slices (see pair_slices_forced above). Results depend on it only
+ * exactly n slices (see g_pair_slices above). Results depend on it only
  * through the summation order. */
 extern "C" void skelly_set_pair_slices(int n) {
-    skelly::g_pair_slices_override = n < 0 ? 0 : n;
+    skelly::g_pair_slices.forced = skelly::g_pair_slices.clamp(n);
 }

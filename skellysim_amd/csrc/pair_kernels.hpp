@@ -1,0 +1,48 @@
+/* pair_kernels.hpp — the one seam between the kernel file (pair_kernels.hip)
+ * and the C-ABI layer (skelly_hip.cpp). Both include it, so a changed
+ * signature fails to compile instead of failing when the library loads. */
+
+#ifndef SKELLY_PAIR_KERNELS_HPP
+#define SKELLY_PAIR_KERNELS_HPP
+
+#include <hip/hip_runtime.h>
+
+namespace skelly {
+
+/* The pair functors of pair_kernels.hip, by name. */
+enum class PairKernel {
+    Stokeslet,
+    Stresslet,
+    OseenContract,
+    Rotlet,
+    StressletNormalDensity,
+    StokesletGrad, /* also the regularized Oseen gradient (reg, eps != 0) */
+    StressletGrad,
+    RotletGrad,
+};
+
+/* Doubles per source of the strength array and per target of the output
+ * (K::SRCDIM, K::OUTDIM). */
+struct PairDims {
+    int srcdim;
+    int outdim;
+};
+PairDims pair_kernel_dims(PairKernel kernel);
+
+/* One launch of `kernel` on device pointers: f_src is (n_src, srcdim), out
+ * (n_trg, outdim). scale is the kernel's prefactor as the caller computed it;
+ * reg and eps are read by the regularized functors only (K::make_params). */
+hipError_t launch_pair_kernel(PairKernel kernel, const double *r_src, const double *f_src,
+                              const double *r_trg, double *out, long long n_src, long long n_trg,
+                              double scale, double reg, double eps, hipStream_t stream);
+
+/* Dense builders and the fp64 peak microbenchmark. */
+hipError_t launch_oseen_tensor_batched(const double *pts, double *G, long long nf, long long n,
+                                       double eta, double reg, double eps, hipStream_t stream);
+hipError_t launch_stresslet_times_normal(const double *pts, const double *normals, double *G,
+                                         long long n, double reg, double eps, hipStream_t stream);
+hipError_t run_fp64_peak(double *out_tflops);
+
+} // namespace skelly
+
+#endif /* SKELLY_PAIR_KERNELS_HPP */

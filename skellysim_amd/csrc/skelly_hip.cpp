@@ -18,30 +18,9 @@
 #include <mutex>
 #include <string>
 
-namespace skelly {
-hipError_t launch_stokeslet(const double *, const double *, const double *, double *, long long,
-                            long long, double, hipStream_t);
-hipError_t launch_stresslet(const double *, const double *, const double *, double *, long long,
-                            long long, double, hipStream_t);
-hipError_t launch_oseen(const double *, const double *, const double *, double *, long long,
-                        long long, double, double, double, hipStream_t);
-hipError_t launch_rotlet(const double *, const double *, const double *, double *, long long,
-                         long long, double, double, double, hipStream_t);
-hipError_t launch_stresslet_normal_density(const double *, const double *, const double *,
-                                           double *, long long, long long, double, double,
-                                           hipStream_t);
-hipError_t launch_stokeslet_grad(const double *, const double *, const double *, double *,
-                                 long long, long long, double, double, double, hipStream_t);
-hipError_t launch_stresslet_grad(const double *, const double *, const double *, double *,
-                                 long long, long long, double, hipStream_t);
-hipError_t launch_rotlet_grad(const double *, const double *, const double *, double *, long long,
-                              long long, double, double, double, hipStream_t);
-hipError_t launch_oseen_tensor_batched(const double *, double *, long long, long long, double,
-                                       double, double, hipStream_t);
-hipError_t launch_stresslet_times_normal(const double *, const double *, double *, long long,
-                                         double, double, hipStream_t);
-hipError_t run_fp64_peak(double *);
-} // namespace skelly
+#include "pair_kernels.hpp"
+
+using skelly::PairKernel;
 
 namespace {
 
@@ -126,40 +105,58 @@ Context &ctx() {
         }                                                                                          \
     } while (0)
 
-/* Shared host-pointer round trip: upload, launch via `fn`, download, sync.
- * outdim doubles per target come back (3 velocity components, 9 of a gradient). */
-template <typename LaunchFn>
-int host_eval(const char *where, const double *r_src, const double *f_src, int srcdim,
-              long long n_src, const double *r_trg, double *u_trg, long long n_trg,
-              LaunchFn &&fn, int outdim = 3) {
+/* Device-pointer form of one pair kernel: launch on the caller's stream, no
+ * synchronization. scale is the kernel's prefactor as the entry point computed
+ * it; reg and eps reach the regularized kernels only. */
+int pair_device(const char *where, PairKernel kernel, const double *d_r_src,
+                const double *d_f_src, long long n_src, const double *d_r_trg, double *d_out,
+                long long n_trg, double scale, double reg, double eps, void *stream) {
+    CHK(where, skelly::launch_pair_kernel(kernel, d_r_src, d_f_src, d_r_trg, d_out, n_src, n_trg,
+                                          scale, reg, eps, (hipStream_t)stream));
+    return 0;
+}
+
+/* Host-pointer form: upload, launch, download, sync on the library's stream.
+ * The kernel's own widths size the buffers (doubles per source of f_src, per
+ * target of out: 3 velocity components, 9 of a gradient). */
+int pair_host(const char *where, PairKernel kernel, const double *r_src, const double *f_src,
+              long long n_src, const double *r_trg, double *out, long long n_trg, double scale,
+              double reg, double eps) {
     if (n_src < 0 || n_trg < 0) {
         g_last_error = std::string(where) + ": negative size";
         return -1;
     }
     if (n_trg == 0)
         return 0;
+    const skelly::PairDims dims = skelly::pair_kernel_dims(kernel);
+    const size_t src_row = (size_t)dims.srcdim * 8, out_row = (size_t)dims.outdim * 8;
     Context &c = ctx();
     std::lock_guard<std::mutex> lock(c.mu);
     CHK(where, c.ensure_stream());
     double *d_rs = nullptr, *d_fs = nullptr, *d_rt = nullptr, *d_u = nullptr;
     /* hipMalloc(0) quirks avoided: allocate at least 8 bytes */
     CHK(where, c.ensure(Context::R_SRC, (size_t)(n_src ? n_src : 1) * 3 * 8, (void **)&d_rs));
-    CHK(where, c.ensure(Context::F_SRC, (size_t)(n_src ? n_src : 1) * srcdim * 8, (void **)&d_fs));
+    CHK(where, c.ensure(Context::F_SRC, (size_t)(n_src ? n_src : 1) * src_row, (void **)&d_fs));
     CHK(where, c.ensure(Context::R_TRG, (size_t)n_trg * 3 * 8, (void **)&d_rt));
-    CHK(where, c.ensure(Context::U_TRG, (size_t)n_trg * outdim * 8, (void **)&d_u));
+    CHK(where, c.ensure(Context::U_TRG, (size_t)n_trg * out_row, (void **)&d_u));
     if (n_src) {
         CHK(where, hipMemcpyAsync(d_rs, r_src, (size_t)n_src * 3 * 8, hipMemcpyHostToDevice,
                                   c.stream));
-        CHK(where, hipMemcpyAsync(d_fs, f_src, (size_t)n_src * srcdim * 8, hipMemcpyHostToDevice,
+        CHK(where, hipMemcpyAsync(d_fs, f_src, (size_t)n_src * src_row, hipMemcpyHostToDevice,
                                   c.stream));
     }
     CHK(where, hipMemcpyAsync(d_rt, r_trg, (size_t)n_trg * 3 * 8, hipMemcpyHostToDevice, c.stream));
-    CHK(where, fn(d_rs, d_fs, d_rt, d_u, c.stream));
-    CHK(where, hipMemcpyAsync(u_trg, d_u, (size_t)n_trg * outdim * 8, hipMemcpyDeviceToHost,
-                              c.stream));
+    CHK(where, skelly::launch_pair_kernel(kernel, d_rs, d_fs, d_rt, d_u, n_src, n_trg, scale, reg,
+                                          eps, c.stream));
+    CHK(where, hipMemcpyAsync(out, d_u, (size_t)n_trg * out_row, hipMemcpyDeviceToHost, c.stream));
     CHK(where, hipStreamSynchronize(c.stream));
     return 0;
 }
+
+/* The two ways the reference writes the prefactor; they differ in the last
+ * bit for general eta, so each entry point keeps the one it always used. */
+double scale_stokes(double eta) { return kOneOver8Pi / eta; }          /* kernels.cu:59 */
+double scale_oseen(double eta) { return 1.0 / (8.0 * M_PI * eta); }    /* kernels.cpp:94,213 */
 
 } // namespace
 
@@ -201,66 +198,42 @@ int skelly_hip_shutdown(void) {
 
 void stokeslet_direct_gpu_impl(const double *r_src, const double *f_src, int n_src,
                                const double *r_trg, double *u_trg, int n_trg) {
-    host_eval("stokeslet_direct_gpu_impl", r_src, f_src, 3, n_src, r_trg, u_trg, n_trg,
-              [&](const double *rs, const double *fs, const double *rt, double *u,
-                  hipStream_t s) {
-                  return skelly::launch_stokeslet(rs, fs, rt, u, n_src, n_trg, kOneOver8Pi, s);
-              });
+    (void)pair_host("stokeslet_direct_gpu_impl", PairKernel::Stokeslet, r_src, f_src, n_src,
+                    r_trg, u_trg, n_trg, kOneOver8Pi, 0.0, 0.0);
 }
 
 void stresslet_direct_gpu_impl(const double *r_src, const double *f_src, int n_src,
                                const double *r_trg, double *u_trg, int n_trg) {
-    host_eval("stresslet_direct_gpu_impl", r_src, f_src, 9, n_src, r_trg, u_trg, n_trg,
-              [&](const double *rs, const double *fs, const double *rt, double *u,
-                  hipStream_t s) {
-                  return skelly::launch_stresslet(rs, fs, rt, u, n_src, n_trg, kOneOver8Pi, s);
-              });
+    (void)pair_host("stresslet_direct_gpu_impl", PairKernel::Stresslet, r_src, f_src, n_src,
+                    r_trg, u_trg, n_trg, kOneOver8Pi, 0.0, 0.0);
 }
 
 /* ---- extended host-pointer API (fully scaled) ---- */
 
 int skelly_stokeslet_host(const double *r_src, const double *f_src, long long n_src,
                           const double *r_trg, double *u_trg, long long n_trg, double eta) {
-    return host_eval("skelly_stokeslet_host", r_src, f_src, 3, n_src, r_trg, u_trg, n_trg,
-                     [&](const double *rs, const double *fs, const double *rt, double *u,
-                         hipStream_t s) {
-                         return skelly::launch_stokeslet(rs, fs, rt, u, n_src, n_trg,
-                                                         kOneOver8Pi / eta, s);
-                     });
+    return pair_host("skelly_stokeslet_host", PairKernel::Stokeslet, r_src, f_src, n_src, r_trg,
+                     u_trg, n_trg, scale_stokes(eta), 0.0, 0.0);
 }
 
 int skelly_stresslet_host(const double *r_src, const double *f_src, long long n_src,
                           const double *r_trg, double *u_trg, long long n_trg, double eta) {
-    return host_eval("skelly_stresslet_host", r_src, f_src, 9, n_src, r_trg, u_trg, n_trg,
-                     [&](const double *rs, const double *fs, const double *rt, double *u,
-                         hipStream_t s) {
-                         return skelly::launch_stresslet(rs, fs, rt, u, n_src, n_trg,
-                                                         kOneOver8Pi / eta, s);
-                     });
+    return pair_host("skelly_stresslet_host", PairKernel::Stresslet, r_src, f_src, n_src, r_trg,
+                     u_trg, n_trg, scale_stokes(eta), 0.0, 0.0);
 }
 
 int skelly_oseen_contract_host(const double *r_src, const double *r_trg, const double *density,
                                double *u_trg, long long n_src, long long n_trg, double eta,
                                double reg, double epsilon_distance) {
-    const double factor = 1.0 / (8.0 * M_PI * eta); /* kernels.cpp:94 */
-    return host_eval("skelly_oseen_contract_host", r_src, density, 3, n_src, r_trg, u_trg, n_trg,
-                     [&](const double *rs, const double *ds, const double *rt, double *u,
-                         hipStream_t s) {
-                         return skelly::launch_oseen(rs, ds, rt, u, n_src, n_trg, factor, reg,
-                                                     epsilon_distance, s);
-                     });
+    return pair_host("skelly_oseen_contract_host", PairKernel::OseenContract, r_src, density,
+                     n_src, r_trg, u_trg, n_trg, scale_oseen(eta), reg, epsilon_distance);
 }
 
 int skelly_rotlet_host(const double *r_src, const double *r_trg, const double *density,
                        double *u_trg, long long n_src, long long n_trg, double eta, double reg,
                        double epsilon_distance) {
-    const double factor = 1.0 / (8.0 * M_PI * eta); /* kernels.cpp:213 */
-    return host_eval("skelly_rotlet_host", r_src, density, 3, n_src, r_trg, u_trg, n_trg,
-                     [&](const double *rs, const double *ds, const double *rt, double *u,
-                         hipStream_t s) {
-                         return skelly::launch_rotlet(rs, ds, rt, u, n_src, n_trg, factor, reg,
-                                                      epsilon_distance, s);
-                     });
+    return pair_host("skelly_rotlet_host", PairKernel::Rotlet, r_src, density, n_src, r_trg,
+                     u_trg, n_trg, scale_oseen(eta), reg, epsilon_distance);
 }
 
 /* ---- device-pointer API (async on caller's stream) ---- */
@@ -268,133 +241,99 @@ int skelly_rotlet_host(const double *r_src, const double *r_trg, const double *d
 int skelly_stokeslet_device(const double *d_r_src, const double *d_f_src, long long n_src,
                             const double *d_r_trg, double *d_u_trg, long long n_trg, double eta,
                             void *stream) {
-    CHK("skelly_stokeslet_device",
-        skelly::launch_stokeslet(d_r_src, d_f_src, d_r_trg, d_u_trg, n_src, n_trg,
-                                 kOneOver8Pi / eta, (hipStream_t)stream));
-    return 0;
+    return pair_device("skelly_stokeslet_device", PairKernel::Stokeslet, d_r_src, d_f_src, n_src,
+                       d_r_trg, d_u_trg, n_trg, scale_stokes(eta), 0.0, 0.0, stream);
 }
 
 int skelly_stresslet_device(const double *d_r_src, const double *d_f_src, long long n_src,
                             const double *d_r_trg, double *d_u_trg, long long n_trg, double eta,
                             void *stream) {
-    CHK("skelly_stresslet_device",
-        skelly::launch_stresslet(d_r_src, d_f_src, d_r_trg, d_u_trg, n_src, n_trg,
-                                 kOneOver8Pi / eta, (hipStream_t)stream));
-    return 0;
+    return pair_device("skelly_stresslet_device", PairKernel::Stresslet, d_r_src, d_f_src, n_src,
+                       d_r_trg, d_u_trg, n_trg, scale_stokes(eta), 0.0, 0.0, stream);
 }
 
 int skelly_oseen_contract_device(const double *d_r_src, const double *d_r_trg,
                                  const double *d_density, double *d_u_trg, long long n_src,
                                  long long n_trg, double eta, double reg, double epsilon_distance,
                                  void *stream) {
-    const double factor = 1.0 / (8.0 * M_PI * eta);
-    CHK("skelly_oseen_contract_device",
-        skelly::launch_oseen(d_r_src, d_density, d_r_trg, d_u_trg, n_src, n_trg, factor, reg,
-                             epsilon_distance, (hipStream_t)stream));
-    return 0;
+    return pair_device("skelly_oseen_contract_device", PairKernel::OseenContract, d_r_src,
+                       d_density, n_src, d_r_trg, d_u_trg, n_trg, scale_oseen(eta), reg,
+                       epsilon_distance, stream);
 }
 
 int skelly_rotlet_device(const double *d_r_src, const double *d_r_trg, const double *d_density,
                          double *d_u_trg, long long n_src, long long n_trg, double eta, double reg,
                          double epsilon_distance, void *stream) {
-    const double factor = 1.0 / (8.0 * M_PI * eta);
-    CHK("skelly_rotlet_device",
-        skelly::launch_rotlet(d_r_src, d_density, d_r_trg, d_u_trg, n_src, n_trg, factor, reg,
-                              epsilon_distance, (hipStream_t)stream));
-    return 0;
+    return pair_device("skelly_rotlet_device", PairKernel::Rotlet, d_r_src, d_density, n_src,
+                       d_r_trg, d_u_trg, n_trg, scale_oseen(eta), reg, epsilon_distance, stream);
 }
 
-/* ---- velocity gradients: 9 doubles per target, G[i][j] at 9*it + 3*i + j ---- */
+/* ---- velocity gradients: 9 doubles per target, G[i][j] at 9*it + 3*i + j ----
+ * The oseen forms run StokesletGrad with the regularization switched on. */
 
 int skelly_stokeslet_grad_host(const double *r_src, const double *f_src, long long n_src,
                                const double *r_trg, double *g_trg, long long n_trg, double eta) {
-    return host_eval("skelly_stokeslet_grad_host", r_src, f_src, 3, n_src, r_trg, g_trg, n_trg,
-                     [&](const double *rs, const double *fs, const double *rt, double *g,
-                         hipStream_t s) {
-                         return skelly::launch_stokeslet_grad(rs, fs, rt, g, n_src, n_trg,
-                                                              kOneOver8Pi / eta, 0.0, 0.0, s);
-                     },
-                     9);
+    return pair_host("skelly_stokeslet_grad_host", PairKernel::StokesletGrad, r_src, f_src, n_src,
+                     r_trg, g_trg, n_trg, scale_stokes(eta), 0.0, 0.0);
 }
 
 int skelly_stresslet_grad_host(const double *r_src, const double *f_src, long long n_src,
                                const double *r_trg, double *g_trg, long long n_trg, double eta) {
-    return host_eval("skelly_stresslet_grad_host", r_src, f_src, 9, n_src, r_trg, g_trg, n_trg,
-                     [&](const double *rs, const double *fs, const double *rt, double *g,
-                         hipStream_t s) {
-                         return skelly::launch_stresslet_grad(rs, fs, rt, g, n_src, n_trg,
-                                                              kOneOver8Pi / eta, s);
-                     },
-                     9);
+    return pair_host("skelly_stresslet_grad_host", PairKernel::StressletGrad, r_src, f_src, n_src,
+                     r_trg, g_trg, n_trg, scale_stokes(eta), 0.0, 0.0);
 }
 
 int skelly_oseen_contract_grad_host(const double *r_src, const double *r_trg,
                                     const double *density, double *g_trg, long long n_src,
                                     long long n_trg, double eta, double reg,
                                     double epsilon_distance) {
-    const double factor = 1.0 / (8.0 * M_PI * eta);
-    return host_eval("skelly_oseen_contract_grad_host", r_src, density, 3, n_src, r_trg, g_trg,
-                     n_trg,
-                     [&](const double *rs, const double *ds, const double *rt, double *g,
-                         hipStream_t s) {
-                         return skelly::launch_stokeslet_grad(rs, ds, rt, g, n_src, n_trg, factor,
-                                                              reg, epsilon_distance, s);
-                     },
-                     9);
+    return pair_host("skelly_oseen_contract_grad_host", PairKernel::StokesletGrad, r_src, density,
+                     n_src, r_trg, g_trg, n_trg, scale_oseen(eta), reg, epsilon_distance);
 }
 
 int skelly_rotlet_grad_host(const double *r_src, const double *r_trg, const double *density,
                             double *g_trg, long long n_src, long long n_trg, double eta,
                             double reg, double epsilon_distance) {
-    const double factor = 1.0 / (8.0 * M_PI * eta);
-    return host_eval("skelly_rotlet_grad_host", r_src, density, 3, n_src, r_trg, g_trg, n_trg,
-                     [&](const double *rs, const double *ds, const double *rt, double *g,
-                         hipStream_t s) {
-                         return skelly::launch_rotlet_grad(rs, ds, rt, g, n_src, n_trg, factor,
-                                                           reg, epsilon_distance, s);
-                     },
-                     9);
+    return pair_host("skelly_rotlet_grad_host", PairKernel::RotletGrad, r_src, density, n_src,
+                     r_trg, g_trg, n_trg, scale_oseen(eta), reg, epsilon_distance);
 }
 
 int skelly_stokeslet_grad_device(const double *d_r_src, const double *d_f_src, long long n_src,
                                  const double *d_r_trg, double *d_g_trg, long long n_trg,
                                  double eta, void *stream) {
-    CHK("skelly_stokeslet_grad_device",
-        skelly::launch_stokeslet_grad(d_r_src, d_f_src, d_r_trg, d_g_trg, n_src, n_trg,
-                                      kOneOver8Pi / eta, 0.0, 0.0, (hipStream_t)stream));
-    return 0;
+    return pair_device("skelly_stokeslet_grad_device", PairKernel::StokesletGrad, d_r_src,
+                       d_f_src, n_src, d_r_trg, d_g_trg, n_trg, scale_stokes(eta), 0.0, 0.0,
+                       stream);
 }
 
 int skelly_stresslet_grad_device(const double *d_r_src, const double *d_f_src, long long n_src,
                                  const double *d_r_trg, double *d_g_trg, long long n_trg,
                                  double eta, void *stream) {
-    CHK("skelly_stresslet_grad_device",
-        skelly::launch_stresslet_grad(d_r_src, d_f_src, d_r_trg, d_g_trg, n_src, n_trg,
-                                      kOneOver8Pi / eta, (hipStream_t)stream));
-    return 0;
+    return pair_device("skelly_stresslet_grad_device", PairKernel::StressletGrad, d_r_src,
+                       d_f_src, n_src, d_r_trg, d_g_trg, n_trg, scale_stokes(eta), 0.0, 0.0,
+                       stream);
 }
 
 int skelly_oseen_contract_grad_device(const double *d_r_src, const double *d_r_trg,
                                       const double *d_density, double *d_g_trg, long long n_src,
                                       long long n_trg, double eta, double reg,
                                       double epsilon_distance, void *stream) {
-    const double factor = 1.0 / (8.0 * M_PI * eta);
-    CHK("skelly_oseen_contract_grad_device",
-        skelly::launch_stokeslet_grad(d_r_src, d_density, d_r_trg, d_g_trg, n_src, n_trg, factor,
-                                      reg, epsilon_distance, (hipStream_t)stream));
-    return 0;
+    return pair_device("skelly_oseen_contract_grad_device", PairKernel::StokesletGrad, d_r_src,
+                       d_density, n_src, d_r_trg, d_g_trg, n_trg, scale_oseen(eta), reg,
+                       epsilon_distance, stream);
 }
 
 int skelly_rotlet_grad_device(const double *d_r_src, const double *d_r_trg,
                               const double *d_density, double *d_g_trg, long long n_src,
                               long long n_trg, double eta, double reg, double epsilon_distance,
                               void *stream) {
-    const double factor = 1.0 / (8.0 * M_PI * eta);
-    CHK("skelly_rotlet_grad_device",
-        skelly::launch_rotlet_grad(d_r_src, d_density, d_r_trg, d_g_trg, n_src, n_trg, factor,
-                                   reg, epsilon_distance, (hipStream_t)stream));
-    return 0;
+    return pair_device("skelly_rotlet_grad_device", PairKernel::RotletGrad, d_r_src, d_density,
+                       n_src, d_r_trg, d_g_trg, n_trg, scale_oseen(eta), reg, epsilon_distance,
+                       stream);
 }
+
+/* stresslet x normal x density: the prefactor -3/(4*pi) is the functor's own
+ * (no eta), so the scale argument is not read. */
 
 int skelly_stresslet_normal_density_host(const double *r_src, const double *normals,
                                          const double *density, double *out, long long n,
@@ -407,23 +346,17 @@ int skelly_stresslet_normal_density_host(const double *r_src, const double *norm
             nd[6 * i + 3 + k] = density[3 * i + k];
         }
     }
-    return host_eval("skelly_stresslet_normal_density_host", r_src, nd.data(), 6, n, r_src, out,
-                     n,
-                     [&](const double *rs, const double *fs, const double *rt, double *u,
-                         hipStream_t s) {
-                         return skelly::launch_stresslet_normal_density(
-                             rs, fs, rt, u, n, n, reg, epsilon_distance, s);
-                     });
+    return pair_host("skelly_stresslet_normal_density_host", PairKernel::StressletNormalDensity,
+                     r_src, nd.data(), n, r_src, out, n, 0.0, reg, epsilon_distance);
 }
 
 int skelly_stresslet_normal_density_device(const double *d_r_src, const double *d_nd,
                                            const double *d_r_trg, double *d_out, long long n_src,
                                            long long n_trg, double reg, double epsilon_distance,
                                            void *stream) {
-    CHK("skelly_stresslet_normal_density_device",
-        skelly::launch_stresslet_normal_density(d_r_src, d_nd, d_r_trg, d_out, n_src, n_trg, reg,
-                                                epsilon_distance, (hipStream_t)stream));
-    return 0;
+    return pair_device("skelly_stresslet_normal_density_device",
+                       PairKernel::StressletNormalDensity, d_r_src, d_nd, n_src, d_r_trg, d_out,
+                       n_trg, 0.0, reg, epsilon_distance, stream);
 }
 
 int skelly_stresslet_times_normal_device(const double *d_pts, const double *d_normals,

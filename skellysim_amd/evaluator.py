@@ -20,12 +20,38 @@ ships no FMM or CPU compute path.
 """
 
 import ctypes
+import math
 
 import numpy as np
 
 from . import _native
 
 _DP = ctypes.POINTER(ctypes.c_double)
+
+class _Pair:
+    """One pair kernel as this module sees it: the entry points
+    skelly_<symbol>_host / skelly_<symbol>_device (argument order:
+    _native.PAIR_FAMILY), the doubles per source of its strength array and the
+    per-target shape of its result. `symbol` is also the _native.check label.
+    Everything a call needs is worked out here, once."""
+
+    def __init__(self, symbol, srcdim, out):
+        self.symbol, self.srcdim, self.out = symbol, srcdim, out
+        self.host, self.device = f"skelly_{symbol}_host", f"skelly_{symbol}_device"
+        self.numel = math.prod(out)
+        self.strength_first = _native.PAIR_FAMILY[symbol] == _native.STRENGTH
+        # argument names for error messages
+        self.names = ("r_src", "f_src" if self.strength_first else "density")
+
+
+_STOKESLET = _Pair("stokeslet", 3, (3,))
+_STRESSLET = _Pair("stresslet", 9, (3,))
+_OSEEN = _Pair("oseen_contract", 3, (3,))
+_ROTLET = _Pair("rotlet", 3, (3,))
+_STOKESLET_GRAD = _Pair("stokeslet_grad", 3, (3, 3))
+_STRESSLET_GRAD = _Pair("stresslet_grad", 9, (3, 3))
+_OSEEN_GRAD = _Pair("oseen_contract_grad", 3, (3, 3))
+_ROTLET_GRAD = _Pair("rotlet_grad", 3, (3, 3))
 
 
 def _rows(a, dim, name):
@@ -49,57 +75,49 @@ def _ptr(a):
     return a.ctypes.data_as(_DP)
 
 
+def _pair_args(k, r_src, f_src, n_src, r_trg, out, n_trg):
+    """The leading arguments in the order k's entry points take them."""
+    if k.strength_first:
+        return r_src, f_src, n_src, r_trg, out, n_trg
+    return r_src, r_trg, f_src, out, n_src, n_trg
+
+
+def _host_pair(k, r_src, f_src, r_trg, scalars, names=None):
+    """Kernel k on host arrays: normalize, call skelly_<symbol>_host, return
+    (n_trg,) + k.out. `scalars` are the trailing doubles (eta[, reg, eps])."""
+    names = names or k.names
+    src = _rows(r_src, 3, names[0])
+    f = _rows(f_src, k.srcdim, names[1])
+    trg = _rows(r_trg, 3, "r_trg")
+    out = np.zeros((len(trg),) + k.out)
+    fn = getattr(_native.lib(), k.host)
+    rc = fn(*_pair_args(k, _ptr(src), _ptr(f), len(src), _ptr(trg), _ptr(out), len(trg)),
+            *map(float, scalars))
+    _native.check(rc, k.symbol)
+    return out
+
+
 def stokeslet_direct_gpu(r_sl, r_dl, r_trg, f_sl, f_dl, eta):
     """Evaluator-signature Stokeslet (mirrors kernels::stokeslet_direct_gpu,
     src/core/kernels.cpp:361-366): uses (r_sl, f_sl), returns u/eta."""
-    r_src = _rows(r_sl, 3, "r_sl")
-    f_src = _rows(f_sl, 3, "f_sl")
-    trg = _rows(r_trg, 3, "r_trg")
-    u = np.zeros((len(trg), 3))
-    rc = _native.lib().skelly_stokeslet_host(_ptr(r_src), _ptr(f_src), len(r_src),
-                                             _ptr(trg), _ptr(u), len(trg), float(eta))
-    _native.check(rc, "stokeslet")
-    return u
+    return _host_pair(_STOKESLET, r_sl, f_sl, r_trg, (eta,), names=("r_sl", "f_sl"))
 
 
 def stresslet_direct_gpu(r_sl, r_dl, r_trg, f_sl, f_dl, eta):
     """Evaluator-signature stresslet (mirrors kernels::stresslet_direct_gpu,
     src/core/kernels.cpp:354-359): uses (r_dl, f_dl), returns u/eta."""
-    r_src = _rows(r_dl, 3, "r_dl")
-    f_src = _rows(f_dl, 9, "f_dl")
-    trg = _rows(r_trg, 3, "r_trg")
-    u = np.zeros((len(trg), 3))
-    rc = _native.lib().skelly_stresslet_host(_ptr(r_src), _ptr(f_src), len(r_src),
-                                             _ptr(trg), _ptr(u), len(trg), float(eta))
-    _native.check(rc, "stresslet")
-    return u
+    return _host_pair(_STRESSLET, r_dl, f_dl, r_trg, (eta,), names=("r_dl", "f_dl"))
 
 
 def oseen_contract_direct_gpu(r_src, r_trg, density, eta=1.0, reg=5e-3, epsilon_distance=1e-5):
     """Mirrors kernels::oseen_tensor_contract_direct (kernels.cpp:85-131;
     defaults kernels.hpp:34-35)."""
-    src = _rows(r_src, 3, "r_src")
-    trg = _rows(r_trg, 3, "r_trg")
-    rho = _rows(density, 3, "density")
-    u = np.zeros((len(trg), 3))
-    rc = _native.lib().skelly_oseen_contract_host(_ptr(src), _ptr(trg), _ptr(rho), _ptr(u),
-                                                  len(src), len(trg), float(eta), float(reg),
-                                                  float(epsilon_distance))
-    _native.check(rc, "oseen_contract")
-    return u
+    return _host_pair(_OSEEN, r_src, density, r_trg, (eta, reg, epsilon_distance))
 
 
 def rotlet_gpu(r_src, r_trg, density, eta=1.0, reg=5e-3, epsilon_distance=1e-5):
     """Mirrors kernels::rotlet (kernels.cpp:206-242; defaults kernels.hpp:44-45)."""
-    src = _rows(r_src, 3, "r_src")
-    trg = _rows(r_trg, 3, "r_trg")
-    rho = _rows(density, 3, "density")
-    u = np.zeros((len(trg), 3))
-    rc = _native.lib().skelly_rotlet_host(_ptr(src), _ptr(trg), _ptr(rho), _ptr(u),
-                                          len(src), len(trg), float(eta), float(reg),
-                                          float(epsilon_distance))
-    _native.check(rc, "rotlet")
-    return u
+    return _host_pair(_ROTLET, r_src, density, r_trg, (eta, reg, epsilon_distance))
 
 
 # Velocity gradients, host arrays: (n_trg, 3, 3) with G[t, i, j] = du_i/dx_j at
@@ -107,53 +125,23 @@ def rotlet_gpu(r_src, r_trg, density, eta=1.0, reg=5e-3, epsilon_distance=1e-5):
 
 def stokeslet_grad(r_src, f_src, r_trg, eta):
     """Gradient of the Stokeslet velocity (stokeslet_direct_gpu's field)."""
-    src = _rows(r_src, 3, "r_src")
-    f = _rows(f_src, 3, "f_src")
-    trg = _rows(r_trg, 3, "r_trg")
-    g = np.zeros((len(trg), 3, 3))
-    rc = _native.lib().skelly_stokeslet_grad_host(_ptr(src), _ptr(f), len(src), _ptr(trg),
-                                                  _ptr(g), len(trg), float(eta))
-    _native.check(rc, "stokeslet_grad")
-    return g
+    return _host_pair(_STOKESLET_GRAD, r_src, f_src, r_trg, (eta,))
 
 
 def stresslet_grad(r_src, f_src, r_trg, eta):
     """Gradient of the stresslet velocity (stresslet_direct_gpu's field)."""
-    src = _rows(r_src, 3, "r_src")
-    f = _rows(f_src, 9, "f_src")
-    trg = _rows(r_trg, 3, "r_trg")
-    g = np.zeros((len(trg), 3, 3))
-    rc = _native.lib().skelly_stresslet_grad_host(_ptr(src), _ptr(f), len(src), _ptr(trg),
-                                                  _ptr(g), len(trg), float(eta))
-    _native.check(rc, "stresslet_grad")
-    return g
+    return _host_pair(_STRESSLET_GRAD, r_src, f_src, r_trg, (eta,))
 
 
 def oseen_contract_grad(r_src, r_trg, density, eta=1.0, reg=5e-3, epsilon_distance=1e-5):
     """Gradient of oseen_contract_direct_gpu's field (exact inside each branch
     of the regularization)."""
-    src = _rows(r_src, 3, "r_src")
-    trg = _rows(r_trg, 3, "r_trg")
-    rho = _rows(density, 3, "density")
-    g = np.zeros((len(trg), 3, 3))
-    rc = _native.lib().skelly_oseen_contract_grad_host(_ptr(src), _ptr(trg), _ptr(rho), _ptr(g),
-                                                       len(src), len(trg), float(eta),
-                                                       float(reg), float(epsilon_distance))
-    _native.check(rc, "oseen_contract_grad")
-    return g
+    return _host_pair(_OSEEN_GRAD, r_src, density, r_trg, (eta, reg, epsilon_distance))
 
 
 def rotlet_grad(r_src, r_trg, density, eta=1.0, reg=5e-3, epsilon_distance=1e-5):
     """Gradient of rotlet_gpu's field."""
-    src = _rows(r_src, 3, "r_src")
-    trg = _rows(r_trg, 3, "r_trg")
-    rho = _rows(density, 3, "density")
-    g = np.zeros((len(trg), 3, 3))
-    rc = _native.lib().skelly_rotlet_grad_host(_ptr(src), _ptr(trg), _ptr(rho), _ptr(g),
-                                               len(src), len(trg), float(eta), float(reg),
-                                               float(epsilon_distance))
-    _native.check(rc, "rotlet_grad")
-    return g
+    return _host_pair(_ROTLET_GRAD, r_src, density, r_trg, (eta, reg, epsilon_distance))
 
 
 class Evaluator:
@@ -212,57 +200,57 @@ def _dev_rows(t, dim, name):
     return t.contiguous()
 
 
+def _dev_out(out, r_trg, shape, numel):
+    """The result tensor (n_trg,) + shape: a fresh one, or the caller's `out`
+    if the kernel can write it as is."""
+    import torch
+    n_trg = r_trg.shape[0]  # (len() of a tensor costs several times this)
+    if out is None:
+        return torch.empty((n_trg,) + shape, dtype=torch.float64, device=r_trg.device)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64
+            and out.is_contiguous() and out.numel() == n_trg * numel):
+        raise ValueError("out: expected a contiguous float64 CUDA tensor of "
+                         f"(n_trg, {', '.join(map(str, shape))})")
+    return out
+
+
+def _dptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
 def _stream_ptr():
     import torch
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _device_pair(k, r_src, f_src, r_trg, out, scalars):
+    """Kernel k on device tensors, async on torch's current stream: validate,
+    call skelly_<symbol>_device, return `out` ((n_trg,) + k.out)."""
+    r_src = _dev_rows(r_src, 3, "r_src")
+    f_src = _dev_rows(f_src, k.srcdim, k.names[1])
+    r_trg = _dev_rows(r_trg, 3, "r_trg")
+    out = _dev_out(out, r_trg, k.out, k.numel)
+    fn = getattr(_native.lib(), k.device)
+    rc = fn(*_pair_args(k, _dptr(r_src), _dptr(f_src), r_src.shape[0], _dptr(r_trg), _dptr(out),
+                        r_trg.shape[0]),
+            *map(float, scalars), _stream_ptr())
+    _native.check(rc, k.symbol + "_device")
+    return out
+
+
 def stokeslet_device(r_src, f_src, r_trg, eta, out=None):
     """Stokeslet on device tensors (n,3); returns (n_trg,3) velocities
     (fully scaled 1/(8 pi eta)). Async on torch's current stream."""
-    import torch
-    r_src = _dev_rows(r_src, 3, "r_src")
-    f_src = _dev_rows(f_src, 3, "f_src")
-    r_trg = _dev_rows(r_trg, 3, "r_trg")
-    if out is None:
-        out = torch.empty_like(r_trg)
-    rc = _native.lib().skelly_stokeslet_device(
-        ctypes.c_void_p(r_src.data_ptr()), ctypes.c_void_p(f_src.data_ptr()), len(r_src),
-        ctypes.c_void_p(r_trg.data_ptr()), ctypes.c_void_p(out.data_ptr()), len(r_trg),
-        float(eta), _stream_ptr())
-    _native.check(rc, "stokeslet_device")
-    return out
+    return _device_pair(_STOKESLET, r_src, f_src, r_trg, out, (eta,))
 
 
 def stresslet_device(r_src, f_src, r_trg, eta, out=None):
-    import torch
-    r_src = _dev_rows(r_src, 3, "r_src")
-    f_src = _dev_rows(f_src, 9, "f_src")
-    r_trg = _dev_rows(r_trg, 3, "r_trg")
-    if out is None:
-        out = torch.empty_like(r_trg)
-    rc = _native.lib().skelly_stresslet_device(
-        ctypes.c_void_p(r_src.data_ptr()), ctypes.c_void_p(f_src.data_ptr()), len(r_src),
-        ctypes.c_void_p(r_trg.data_ptr()), ctypes.c_void_p(out.data_ptr()), len(r_trg),
-        float(eta), _stream_ptr())
-    _native.check(rc, "stresslet_device")
-    return out
+    return _device_pair(_STRESSLET, r_src, f_src, r_trg, out, (eta,))
 
 
 def oseen_contract_device(r_src, r_trg, density, eta=1.0, reg=5e-3, epsilon_distance=1e-5,
                           out=None):
-    import torch
-    r_src = _dev_rows(r_src, 3, "r_src")
-    r_trg = _dev_rows(r_trg, 3, "r_trg")
-    density = _dev_rows(density, 3, "density")
-    if out is None:
-        out = torch.empty_like(r_trg)
-    rc = _native.lib().skelly_oseen_contract_device(
-        ctypes.c_void_p(r_src.data_ptr()), ctypes.c_void_p(r_trg.data_ptr()),
-        ctypes.c_void_p(density.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-        len(r_src), len(r_trg), float(eta), float(reg), float(epsilon_distance), _stream_ptr())
-    _native.check(rc, "oseen_contract_device")
-    return out
+    return _device_pair(_OSEEN, r_src, density, r_trg, out, (eta, reg, epsilon_distance))
 
 
 def stresslet_normal_density_device(r_src, normals, density, r_trg=None, reg=5e-3,
@@ -275,12 +263,10 @@ def stresslet_normal_density_device(r_src, normals, density, r_trg=None, reg=5e-
     density = _dev_rows(density, 3, "density")
     r_trg = r_src if r_trg is None else _dev_rows(r_trg, 3, "r_trg")
     nd = torch.cat([normals, density], dim=1).contiguous()
-    if out is None:
-        out = torch.empty_like(r_trg)
+    out = _dev_out(out, r_trg, (3,), 3)
     rc = _native.lib().skelly_stresslet_normal_density_device(
-        ctypes.c_void_p(r_src.data_ptr()), ctypes.c_void_p(nd.data_ptr()),
-        ctypes.c_void_p(r_trg.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-        len(r_src), len(r_trg), float(reg), float(epsilon_distance), _stream_ptr())
+        _dptr(r_src), _dptr(nd), _dptr(r_trg), _dptr(out), len(r_src), len(r_trg),
+        float(reg), float(epsilon_distance), _stream_ptr())
     _native.check(rc, "stresslet_normal_density_device")
     return out
 
@@ -295,8 +281,8 @@ def stresslet_times_normal_device(pts, normals, reg=5e-3, epsilon_distance=1e-5,
     if out is None:
         out = torch.empty((3 * n, 3 * n), dtype=torch.float64, device=pts.device)
     rc = _native.lib().skelly_stresslet_times_normal_device(
-        ctypes.c_void_p(pts.data_ptr()), ctypes.c_void_p(normals.data_ptr()),
-        ctypes.c_void_p(out.data_ptr()), n, float(reg), float(epsilon_distance), _stream_ptr())
+        _dptr(pts), _dptr(normals), _dptr(out), n, float(reg), float(epsilon_distance),
+        _stream_ptr())
     _native.check(rc, "stresslet_times_normal_device")
     return out
 
@@ -314,94 +300,37 @@ def oseen_tensor_batched_device(pts, eta=1.0, reg=5e-3, epsilon_distance=1e-5, o
     if out is None:
         out = torch.empty((nf, 3 * n, 3 * n), dtype=torch.float64, device=pts.device)
     rc = _native.lib().skelly_oseen_tensor_batched_device(
-        ctypes.c_void_p(pts.data_ptr()), ctypes.c_void_p(out.data_ptr()), nf, n,
-        float(eta), float(reg), float(epsilon_distance), _stream_ptr())
+        _dptr(pts), _dptr(out), nf, n, float(eta), float(reg), float(epsilon_distance),
+        _stream_ptr())
     _native.check(rc, "oseen_tensor_batched_device")
     return out
 
 
 def rotlet_device(r_src, r_trg, density, eta=1.0, reg=5e-3, epsilon_distance=1e-5, out=None):
-    import torch
-    r_src = _dev_rows(r_src, 3, "r_src")
-    r_trg = _dev_rows(r_trg, 3, "r_trg")
-    density = _dev_rows(density, 3, "density")
-    if out is None:
-        out = torch.empty_like(r_trg)
-    rc = _native.lib().skelly_rotlet_device(
-        ctypes.c_void_p(r_src.data_ptr()), ctypes.c_void_p(r_trg.data_ptr()),
-        ctypes.c_void_p(density.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-        len(r_src), len(r_trg), float(eta), float(reg), float(epsilon_distance), _stream_ptr())
-    _native.check(rc, "rotlet_device")
-    return out
+    return _device_pair(_ROTLET, r_src, density, r_trg, out, (eta, reg, epsilon_distance))
 
 
 # ---------------------------------------------------------------------------
 # velocity gradients on device tensors: (n_trg, 3, 3), G[t, i, j] = du_i/dx_j
 # ---------------------------------------------------------------------------
 
-def _grad_out(r_trg, out):
-    import torch
-    if out is None:
-        return torch.empty((len(r_trg), 3, 3), dtype=torch.float64, device=r_trg.device)
-    if not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()
-            and out.numel() == 9 * len(r_trg)):
-        raise ValueError("out: expected a contiguous float64 CUDA tensor of (n_trg, 3, 3)")
-    return out
-
-
 def stokeslet_grad_device(r_src, f_src, r_trg, eta, out=None):
     """Gradient of stokeslet_device's field. Async on torch's current stream."""
-    r_src = _dev_rows(r_src, 3, "r_src")
-    f_src = _dev_rows(f_src, 3, "f_src")
-    r_trg = _dev_rows(r_trg, 3, "r_trg")
-    out = _grad_out(r_trg, out)
-    rc = _native.lib().skelly_stokeslet_grad_device(
-        ctypes.c_void_p(r_src.data_ptr()), ctypes.c_void_p(f_src.data_ptr()), len(r_src),
-        ctypes.c_void_p(r_trg.data_ptr()), ctypes.c_void_p(out.data_ptr()), len(r_trg),
-        float(eta), _stream_ptr())
-    _native.check(rc, "stokeslet_grad_device")
-    return out
+    return _device_pair(_STOKESLET_GRAD, r_src, f_src, r_trg, out, (eta,))
 
 
 def stresslet_grad_device(r_src, f_src, r_trg, eta, out=None):
     """Gradient of stresslet_device's field."""
-    r_src = _dev_rows(r_src, 3, "r_src")
-    f_src = _dev_rows(f_src, 9, "f_src")
-    r_trg = _dev_rows(r_trg, 3, "r_trg")
-    out = _grad_out(r_trg, out)
-    rc = _native.lib().skelly_stresslet_grad_device(
-        ctypes.c_void_p(r_src.data_ptr()), ctypes.c_void_p(f_src.data_ptr()), len(r_src),
-        ctypes.c_void_p(r_trg.data_ptr()), ctypes.c_void_p(out.data_ptr()), len(r_trg),
-        float(eta), _stream_ptr())
-    _native.check(rc, "stresslet_grad_device")
-    return out
+    return _device_pair(_STRESSLET_GRAD, r_src, f_src, r_trg, out, (eta,))
 
 
 def oseen_contract_grad_device(r_src, r_trg, density, eta=1.0, reg=5e-3,
                                epsilon_distance=1e-5, out=None):
     """Gradient of oseen_contract_device's field."""
-    r_src = _dev_rows(r_src, 3, "r_src")
-    r_trg = _dev_rows(r_trg, 3, "r_trg")
-    density = _dev_rows(density, 3, "density")
-    out = _grad_out(r_trg, out)
-    rc = _native.lib().skelly_oseen_contract_grad_device(
-        ctypes.c_void_p(r_src.data_ptr()), ctypes.c_void_p(r_trg.data_ptr()),
-        ctypes.c_void_p(density.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-        len(r_src), len(r_trg), float(eta), float(reg), float(epsilon_distance), _stream_ptr())
-    _native.check(rc, "oseen_contract_grad_device")
-    return out
+    return _device_pair(_OSEEN_GRAD, r_src, density, r_trg, out, (eta, reg, epsilon_distance))
 
 
 def rotlet_grad_device(r_src, r_trg, density, eta=1.0, reg=5e-3, epsilon_distance=1e-5,
                        out=None):
     """Gradient of rotlet_device's field."""
-    r_src = _dev_rows(r_src, 3, "r_src")
-    r_trg = _dev_rows(r_trg, 3, "r_trg")
-    density = _dev_rows(density, 3, "density")
-    out = _grad_out(r_trg, out)
-    rc = _native.lib().skelly_rotlet_grad_device(
-        ctypes.c_void_p(r_src.data_ptr()), ctypes.c_void_p(r_trg.data_ptr()),
-        ctypes.c_void_p(density.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-        len(r_src), len(r_trg), float(eta), float(reg), float(epsilon_distance), _stream_ptr())
-    _native.check(rc, "rotlet_grad_device")
-    return out
+    return _device_pair(_ROTLET_GRAD, r_src, density, r_trg, out, (eta, reg, epsilon_distance))

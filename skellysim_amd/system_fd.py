@@ -43,77 +43,58 @@ class HipBackend:
             return a.to(self.dev)
         return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
 
-    def stokeslet(self, r_src, f_src, r_trg, eta):
-        from .evaluator import stokeslet_device
-        u = stokeslet_device(self._t(r_src), self._t(f_src), self._t(r_trg), eta)
+    def _eval(self, name, arrays, *scalars, **kw):
+        """evaluator.<name>(*arrays on the device, *scalars, **kw), synchronized,
+        as numpy. The function is looked up on each call, so tests can
+        replace it in the module."""
+        from . import evaluator
+        out = getattr(evaluator, name)(*[self._t(a) for a in arrays], *scalars, **kw)
         self.torch.cuda.synchronize()
-        return u.cpu().numpy()
+        return out.cpu().numpy()
+
+    @staticmethod
+    def _f_dl(normals, density, eta):
+        """Shell/body double layer: f_dl = 2*eta*n (x) d, then stresslet/eta
+        (periphery.cpp:68-74)."""
+        return 2.0 * eta * np.einsum("ni,nj->nij", normals, density).reshape(-1, 9)
+
+    def stokeslet(self, r_src, f_src, r_trg, eta):
+        return self._eval("stokeslet_device", (r_src, f_src, r_trg), eta)
 
     def stresslet_normal_density(self, r_src, normals, density, r_trg, eta):
-        """Shell/body double layer: f_dl = 2*eta*n (x) d then stresslet/eta
-        (periphery.cpp:68-74)."""
-        from .evaluator import stresslet_device
-        f_dl = 2.0 * eta * np.einsum("ni,nj->nij", normals, density).reshape(-1, 9)
-        u = stresslet_device(self._t(r_src), self._t(f_dl), self._t(r_trg), eta)
-        self.torch.cuda.synchronize()
-        return u.cpu().numpy()
+        return self._eval("stresslet_device",
+                          (r_src, self._f_dl(normals, density, eta), r_trg), eta)
 
     def self_stokeslet_batch(self, pts, eta):
         """(nf, n, 3) -> (nf, 3n, 3n) oseen_tensor_direct per fiber."""
-        from .evaluator import oseen_tensor_batched_device
-        G = oseen_tensor_batched_device(self._t(pts), eta=eta)
-        self.torch.cuda.synchronize()
-        return G.cpu().numpy()
+        return self._eval("oseen_tensor_batched_device", (pts,), eta=eta)
 
     def rotlet(self, centers, torques, r_trg, eta):
-        from .evaluator import rotlet_device
-        u = rotlet_device(self._t(centers), self._t(r_trg), self._t(torques), eta)
-        self.torch.cuda.synchronize()
-        return u.cpu().numpy()
+        return self._eval("rotlet_device", (centers, r_trg, torques), eta)
 
     def oseen_contract(self, r_src, r_trg, density, eta):
-        from .evaluator import oseen_contract_device
-        u = oseen_contract_device(self._t(r_src), self._t(r_trg),
-                                  self._t(density), eta)
-        self.torch.cuda.synchronize()
-        return u.cpu().numpy()
+        return self._eval("oseen_contract_device", (r_src, r_trg, density), eta)
 
     # velocity gradients: (n_trg, 3, 3), G[t, i, j] = du_i/dx_j
 
     def stokeslet_grad(self, r_src, f_src, r_trg, eta):
-        from .evaluator import stokeslet_grad_device
-        g = stokeslet_grad_device(self._t(r_src), self._t(f_src), self._t(r_trg), eta)
-        self.torch.cuda.synchronize()
-        return g.cpu().numpy()
+        return self._eval("stokeslet_grad_device", (r_src, f_src, r_trg), eta)
 
     def stresslet_normal_density_grad(self, r_src, normals, density, r_trg, eta):
         """Gradient of stresslet_normal_density's field (same f_dl)."""
-        from .evaluator import stresslet_grad_device
-        f_dl = 2.0 * eta * np.einsum("ni,nj->nij", normals, density).reshape(-1, 9)
-        g = stresslet_grad_device(self._t(r_src), self._t(f_dl), self._t(r_trg), eta)
-        self.torch.cuda.synchronize()
-        return g.cpu().numpy()
+        return self._eval("stresslet_grad_device",
+                          (r_src, self._f_dl(normals, density, eta), r_trg), eta)
 
     def rotlet_grad(self, centers, torques, r_trg, eta):
-        from .evaluator import rotlet_grad_device
-        g = rotlet_grad_device(self._t(centers), self._t(r_trg), self._t(torques), eta)
-        self.torch.cuda.synchronize()
-        return g.cpu().numpy()
+        return self._eval("rotlet_grad_device", (centers, r_trg, torques), eta)
 
     def oseen_contract_grad(self, r_src, r_trg, density, eta):
-        from .evaluator import oseen_contract_grad_device
-        g = oseen_contract_grad_device(self._t(r_src), self._t(r_trg),
-                                       self._t(density), eta)
-        self.torch.cuda.synchronize()
-        return g.cpu().numpy()
+        return self._eval("oseen_contract_grad_device", (r_src, r_trg, density), eta)
 
     def stresslet_times_normal(self, nodes, normals, eta):
         """Dense (3n, 3n) operator (kernels.cpp:264-287; eta-independent
         factor) — the M block of the body preconditioner."""
-        from .evaluator import stresslet_times_normal_device
-        S = stresslet_times_normal_device(self._t(nodes), self._t(normals))
-        self.torch.cuda.synchronize()
-        return S.cpu().numpy()
+        return self._eval("stresslet_times_normal_device", (nodes, normals))
 
     def batched_lu(self, A_batch):
         """Factor (nf, m, m); returns solve(rhs_batch (nf, m)) -> (nf, m)."""

@@ -12,12 +12,39 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "skelly_hip.h")
 
 
-def declared_functions():
-    """Function names declared in include/skelly_hip.h."""
+def declared_arity():
+    """{function name: parameter count} of the prototypes in include/skelly_hip.h."""
     src = open(HEADER).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    names = re.findall(r"^\s*(?:const\s+char\s*\*|int|void)\s+(\w+)\s*\(", src, re.M)
-    return [n for n in names if n != "SKELLY_HIP_H"]
+    protos = re.findall(r"^\s*(?:const\s+char\s*\*\s*|int\s+|void\s+)(\w+)\s*\(([^)]*)\)\s*;",
+                        src, re.M)
+    return {name: 0 if params.strip() == "void" else params.count(",") + 1
+            for name, params in protos}
+
+
+def declared_functions():
+    """Function names declared in include/skelly_hip.h."""
+    return list(declared_arity())
+
+
+def test_native_binds_exactly_the_header():
+    """_native binds every function the header declares, with as many argtypes
+    as the prototype has parameters, and binds nothing else."""
+    from skellysim_amd import _native
+    arity = declared_arity()
+    assert sorted(_native.SIGNATURES) == sorted(arity)
+    wrong = {n: (len(_native.SIGNATURES[n][1]), arity[n]) for n in arity
+             if len(_native.SIGNATURES[n][1]) != arity[n]}
+    assert not wrong, f"(bound, declared) parameter counts differ: {wrong}"
+
+
+def test_bind_sets_every_signature(hip_lib_path):
+    from skellysim_amd import _native
+    lib = ctypes.CDLL(hip_lib_path)
+    _native._bind(lib)
+    for name, (restype, argtypes) in _native.SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
 
 
 def test_header_declares_dropin_entry_points():

@@ -252,6 +252,97 @@ def test_device_api_matches_host_api(ska, golden):
     assert np.array_equal(u_dev.cpu().numpy(), u_host)
 
 
+# (host function, device function, source-strength key) of the kernels that
+# take (r_src, strength, r_trg, eta) and of those that take
+# (r_src, r_trg, density, eta, reg, eps); the last pair has its own signature.
+HOST_DEVICE_PAIRS = {
+    "stokeslet": ("stokeslet_direct_gpu", "stokeslet_device", "f3"),
+    "stresslet": ("stresslet_direct_gpu", "stresslet_device", "f9"),
+    "oseen_contract": ("oseen_contract_direct_gpu", "oseen_contract_device", "f3"),
+    "rotlet": ("rotlet_gpu", "rotlet_device", "f3"),
+    "stokeslet_grad": ("stokeslet_grad", "stokeslet_grad_device", "f3"),
+    "stresslet_grad": ("stresslet_grad", "stresslet_grad_device", "f9"),
+    "oseen_contract_grad": ("oseen_contract_grad", "oseen_contract_grad_device", "f3"),
+    "rotlet_grad": ("rotlet_grad", "rotlet_grad_device", "f3"),
+    "stresslet_normal_density": ("stresslet_times_normal_times_density",
+                                 "stresslet_normal_density_device", None),
+}
+
+
+@pytest.mark.parametrize("slices", [0, 3], ids=["planned", "slices3"])
+@pytest.mark.parametrize("kernel", list(HOST_DEVICE_PAIRS))
+def test_device_api_matches_host_api_every_kernel(ska, golden, kernel, slices):
+    """test_device_api_matches_host_api for every kernel, with non-default
+    reg and eps, under the planner's slice count and under a forced one."""
+    import torch
+    from skellysim_amd import _native
+    host_name, dev_name, fkey = HOST_DEVICE_PAIRS[kernel]
+    host_fn, dev_fn = getattr(ska, host_name), getattr(ska, dev_name)
+    eta = float(golden["eta"])
+    dev = torch.device("cuda:0")
+
+    def t(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    r_src, r_trg = golden["r_src"], golden["r_trg"]
+    _native.set_pair_slices(slices)
+    try:
+        if kernel == "stresslet_normal_density":
+            # one point set: sources are the targets
+            nrm, rho = golden["f3"], golden["f9"][:, 2:5]
+            out_dev = dev_fn(t(r_src), t(nrm), t(rho), reg=2e-3, epsilon_distance=3e-5)
+            out_host = host_fn(r_src, nrm, rho, reg=2e-3, epsilon_distance=3e-5)
+        elif kernel in ("stokeslet", "stresslet"):
+            f = golden[fkey]
+            out_dev = dev_fn(t(r_src), t(f), t(r_trg), eta)
+            if kernel == "stokeslet":  # Evaluator signature: (r_sl, r_dl, r_trg, f_sl, f_dl)
+                out_host = host_fn(r_src, None, r_trg, f, None, eta)
+            else:
+                out_host = host_fn(None, r_src, r_trg, None, f, eta)
+        elif kernel in ("stokeslet_grad", "stresslet_grad"):
+            f = golden[fkey]
+            out_dev = dev_fn(t(r_src), t(f), t(r_trg), eta)
+            out_host = host_fn(r_src, f, r_trg, eta)
+        else:
+            f = golden[fkey]
+            out_dev = dev_fn(t(r_src), t(r_trg), t(f), eta, 2e-3, 3e-5)
+            out_host = host_fn(r_src, r_trg, f, eta, 2e-3, 3e-5)
+        torch.cuda.synchronize()
+    finally:
+        _native.set_pair_slices(0)
+    assert out_dev.shape == out_host.shape
+    assert np.isfinite(out_host).all() and np.abs(out_host).max() > 0
+    assert np.array_equal(out_dev.cpu().numpy(), out_host)
+
+
+@pytest.mark.parametrize("dev_name,width", [("stokeslet_device", (3,)),
+                                            ("stokeslet_grad_device", (3, 3))])
+def test_device_out_argument_is_validated(ska, golden, dev_name, width):
+    """out= must be a contiguous float64 CUDA tensor of the result's size:
+    anything else raises instead of being written through; a valid one is
+    filled, returned, and equals the allocating call bitwise."""
+    import torch
+    dev = torch.device("cuda:0")
+    fn = getattr(ska, dev_name)
+    eta = float(golden["eta"])
+    args = [torch.from_numpy(golden[k]).to(dev) for k in ("r_src", "f3", "r_trg")]
+    n_trg = len(golden["r_trg"])
+    ref = fn(*args, eta)
+
+    transposed = torch.empty(width[::-1] + (n_trg,), dtype=torch.float64, device=dev)
+    transposed = transposed.permute(*range(len(width), -1, -1))
+    assert transposed.shape == (n_trg,) + width and not transposed.is_contiguous()
+    with pytest.raises(ValueError):
+        fn(*args, eta, out=transposed)
+    with pytest.raises(ValueError):
+        fn(*args, eta, out=torch.empty((n_trg - 1,) + width, dtype=torch.float64, device=dev))
+
+    out = torch.full((n_trg,) + width, float("nan"), dtype=torch.float64, device=dev)
+    assert fn(*args, eta, out=out) is out
+    torch.cuda.synchronize()
+    assert torch.equal(out, ref)
+
+
 def test_large_cloud_property_checks(ska):
     """At a size where the oracle would be slow, check size-independent
     properties instead: linearity in f and 1/eta scaling (SURVEY §8c tier)."""
