@@ -35,6 +35,13 @@ from .evaluator import (stokeslet_device, stresslet_device, stokeslet_grad_devic
 from .sharded import allgather_rows
 
 
+def double_layer_strength(normals, density, eta):
+    """Stresslet source strength of a double layer, (n, 9) contiguous:
+    f_dl(node)[i*3+j] = 2*eta*normal_i*density_j (periphery.cpp:68-71)."""
+    return (2.0 * eta * torch.einsum("ni,nj->nij", normals, density)
+            ).reshape(-1, 9).contiguous()
+
+
 def periphery_flow(node_pos, node_normal, density, r_trg, eta):
     """Velocity at r_trg due to the shell's double-layer density.
 
@@ -44,8 +51,8 @@ def periphery_flow(node_pos, node_normal, density, r_trg, eta):
     """
     if node_pos.shape[0] == 0:
         return torch.zeros_like(r_trg)
-    f_dl = 2.0 * eta * torch.einsum("ni,nj->nij", node_normal, density).reshape(-1, 9)
-    return stresslet_device(node_pos, f_dl.contiguous(), r_trg, eta)
+    f_dl = double_layer_strength(node_normal, density, eta)
+    return stresslet_device(node_pos, f_dl, r_trg, eta)
 
 
 def fiber_flow(r_src, fib_forces, weights, r_trg, eta, fiber_sizes=None,
@@ -136,8 +143,8 @@ def periphery_flow_grad(node_pos, node_normal, density, r_trg, eta):
     kernel."""
     if node_pos.shape[0] == 0:
         return _zero_grad(r_trg)
-    f_dl = 2.0 * eta * torch.einsum("ni,nj->nij", node_normal, density).reshape(-1, 9)
-    return stresslet_grad_device(node_pos, f_dl.contiguous(), r_trg, eta)
+    f_dl = double_layer_strength(node_normal, density, eta)
+    return stresslet_grad_device(node_pos, f_dl, r_trg, eta)
 
 
 def fiber_flow_grad(r_src, fib_forces, weights, r_trg, eta):

@@ -168,8 +168,10 @@ class SystemFD:
         # dict(kind="sphere"|"ellipsoid", f_0=, l_0=, radius=|abc=) or None
         self.periphery_interaction = periphery_interaction
         self.backend = backend if backend is not None else HipBackend()
-        self._uniform = all(f.n_nodes == self.fibers[0].n_nodes for f in self.fibers) \
-            if self.fibers else True
+        self._uniform = self._fibers_uniform()
+        # (A, F) device tensors of the last prep's batched assembly, when
+        # the backend has a device (_build_device_operators adopts them)
+        self._assembled_dev = None
         if shell is not None:
             self._shell_matvec, self._shell_precond = \
                 self.backend.shell_ops(shell.A, shell.M_inv)
@@ -293,6 +295,10 @@ class SystemFD:
             off += f.n_nodes
         return out
 
+    def _fibers_uniform(self):
+        """All fibers share one discretization (the batched paths apply)."""
+        return all(f.n_nodes == self.fibers[0].n_nodes for f in self.fibers)
+
     # ---- fiber container operations ------------------------------------
     def _build_self_stokeslets(self):
         """Materialize the per-fiber self-stokeslets that prep reset (lazy:
@@ -356,8 +362,7 @@ class SystemFD:
         if self.dynamic_instability:
             from .instability import dynamic_instability
             dynamic_instability(self, self.dynamic_instability, self.rng)
-            self._uniform = all(f.n_nodes == self.fibers[0].n_nodes
-                                for f in self.fibers) if self.fibers else True
+            self._uniform = self._fibers_uniform()
         for f in self.fibers:
             f.update_constants(eta)
             f.update_derivatives()
@@ -436,30 +441,25 @@ class SystemFD:
         if self._uniform and self.fibers:
             # batched assembly (operator + RHS + BCs + force operator) —
             # numerically identical to the per-fiber loop (fiber_batch.py)
-            from .fiber_batch import assemble_uniform, assemble_uniform_t
+            from .fiber_batch import assemble_uniform, install_operators
             n = self.fibers[0].n_nodes
             nf = len(self.fibers)
             flow_b = v_fib.reshape(nf, n, 3).transpose(0, 2, 1)
             motor_b = motor.reshape(nf, n, 3).transpose(0, 2, 1)
             ext_b = ext.reshape(nf, n, 3).transpose(0, 2, 1) \
                 if self.periphery_interaction is not None else None
+            # assemble on the backend's device when it has one (the
+            # dominant prep cost); materialize host copies so the host
+            # matvec/precond paths stay valid, and keep the resident
+            # tensors for _build_device_operators
             dev = getattr(self.backend, "dev", None)
+            A_t, RHS_t, F_t = assemble_uniform(
+                self.fibers, dt, eta, flow=flow_b, f_external=motor_b,
+                bc_force=ext_b, device=dev)
+            install_operators(self.fibers, A_t.cpu().numpy(),
+                              RHS_t.cpu().numpy(), F_t.cpu().numpy())
             if dev is not None:
-                # assemble on device (the dominant prep cost); materialize
-                # host copies so the host matvec/precond paths stay valid,
-                # and keep the resident tensors for _build_device_operators
-                A_t, RHS_t, F_t = assemble_uniform_t(
-                    self.fibers, dt, eta, flow=flow_b, f_external=motor_b,
-                    bc_force=ext_b, device=dev)
-                A_h, R_h, F_h = (A_t.cpu().numpy(), RHS_t.cpu().numpy(),
-                                 F_t.cpu().numpy())
-                for k, f in enumerate(self.fibers):
-                    f.adopt_operator(A_h[k], R_h[k])
-                    f.force_operator = F_h[k]
                 self._assembled_dev = (A_t, F_t)
-            else:
-                assemble_uniform(self.fibers, dt, eta, flow=flow_b,
-                                 f_external=motor_b, bc_force=ext_b)
         else:
             for f, a, b in self._fiber_node_slices():
                 f.update_RHS(dt, v_fib[a:b].T, motor[a:b].T)
@@ -580,14 +580,14 @@ class SystemFD:
         SURVEY.md §8f row 3 in full."""
         import torch
         dev = self.backend.dev
-        T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        T = self.backend._t
 
         nf = len(self.fibers)
         f0 = self.fibers[0]
         n = f0.n_nodes
         self._dev = dict(nf=nf, n=n)
         d = self._dev
-        if getattr(self, "_assembled_dev", None) is not None:
+        if self._assembled_dev is not None:
             d["A"], d["F"] = self._assembled_dev  # already resident from prep
         else:
             d["A"] = T(np.stack([f.A for f in self.fibers]))
@@ -672,6 +672,7 @@ class SystemFD:
         single-rank only."""
         import torch
         from .evaluator import stokeslet_device, stresslet_device
+        from .flows import double_layer_strength
         d = self._dev
         nf, n = d["nf"], d["n"]
         eta = self.eta
@@ -699,8 +700,7 @@ class SystemFD:
             # shell double layer (of the global density) flows to fibers
             # and bodies, not to itself
             dens = self.comm.gather_rows(x_shell.reshape(-1, 3))
-            f_dl = 2.0 * eta * torch.einsum("ni,nj->nij", d["sh_normals"],
-                                            dens).reshape(-1, 9).contiguous()
+            f_dl = double_layer_strength(d["sh_normals"], dens, eta)
             v_all[:nf_nodes] += stresslet_device(d["sh_nodes"], f_dl,
                                                  d["r_fib"], eta)
             if self.bodies:
@@ -751,8 +751,7 @@ class SystemFD:
                 vel7[ai] = torch.cat([v_f, tc[:, None], w_f], dim=1)
 
             # body flow: double layer + center stokeslet/rotlet of link F/T
-            f_dl_b = 2.0 * eta * torch.einsum(
-                "ni,nj->nij", d["body_normals"], bdens).reshape(-1, 9).contiguous()
+            f_dl_b = double_layer_strength(d["body_normals"], bdens, eta)
             v_all += stresslet_device(d["body_nodes"], f_dl_b, d["r_all"], eta)
             v_all += stokeslet_device(d["centers"],
                                       body_ft[:, 0:3].contiguous(),

@@ -192,8 +192,7 @@ def resume_from_trajectory(system, path):
     system.dt = float(frame["dt"])
     _restore_rng(getattr(system, "rng", None), frame.get("rng_state"))
     system.fibers = fibers_from_frame(frame, system.eta)
-    system._uniform = all(f.n_nodes == system.fibers[0].n_nodes
-                          for f in system.fibers) if system.fibers else True
+    system._uniform = system._fibers_uniform()
     body_maps = frame.get("bodies", [[], [], []])[0]
     if len(body_maps) != len(system.bodies):
         raise ValueError("trajectory body count does not match the system")

@@ -7,7 +7,8 @@ flow moves rigidly with the flow
 import numpy as np
 import pytest
 
-from skellysim_amd.fiber_fd import FiberFD, finite_diff, barycentric_matrix, fib_mats
+from skellysim_amd.fiber_fd import (FiberFD, finite_diff, barycentric_matrix, fib_mats,
+                                    BC_VELOCITY, BC_TORQUE)
 from skellysim_amd.system_fd import SystemFD
 from oracle_backend import OracleBackend
 
@@ -65,87 +66,98 @@ def test_derivatives_of_straight_fiber():
     assert np.allclose(f.xssss, 0.0, atol=1e-3)  # 4th derivative noise floor
 
 
-def test_batched_assembly_matches_per_fiber_loop():
-    """fiber_batch.assemble_uniform must reproduce the per-fiber
-    update_linear_operator/update_RHS/apply_bc_rectangular/force_operator
-    results exactly, across mixed BCs."""
-    from skellysim_amd.fiber_batch import assemble_uniform
-    rng = np.random.default_rng(12)
-    dt, eta, n = 0.05, 1.3, 24
-    fibers, flows, motors = [], [], []
-    for k in range(5):
-        f = straight_fiber(n=n, length=0.8 + 0.1 * k,
+ASM_DT, ASM_ETA, ASM_N = 0.05, 1.3, 24
+
+
+def assembly_fibers(rng, minus_clamped, plus_velocity=None):
+    """One ASM_N-node fiber per entry of minus_clamped, with distinct lengths
+    and random poses, prepared for assembly. plus_velocity: per-fiber flags
+    that put the (Velocity, Torque) plus end of a cortex-bound fiber on
+    directly (production reaches it only through periphery binding)."""
+    fibers = []
+    for k, clamped in enumerate(minus_clamped):
+        f = straight_fiber(n=ASM_N, length=0.8 + 0.1 * k,
                            direction=rng.uniform(-1, 1, 3),
-                           x0=rng.uniform(-1, 1, 3),
-                           minus_clamped=(k % 2 == 0))
+                           x0=rng.uniform(-1, 1, 3), minus_clamped=clamped)
         f.force_scale = -0.05
-        f.update_constants(eta)
+        if plus_velocity is not None and plus_velocity[k]:
+            f.bc_plus = (BC_VELOCITY, BC_TORQUE)
+        f.update_constants(ASM_ETA)
         f.update_derivatives()
         fibers.append(f)
-        flows.append(rng.uniform(-1, 1, (3, n)))
-        motors.append(rng.uniform(-1, 1, (3, n)))
+    return fibers
 
+
+def assembly_inputs(rng, nf):
+    """(flow, f_external, bc_force), each (nf, 3, ASM_N)."""
+    return tuple(rng.uniform(-1, 1, (nf, 3, ASM_N)) for _ in range(3))
+
+
+def per_fiber_assembly(fibers, flow=None, f_external=None, bc_force=None):
+    """The oracle of the batched assembly: [(A, RHS, F)] from the per-fiber
+    restatement of the reference."""
+    pick = lambda a, k: None if a is None else a[k]
     refs = []
-    for f, fl, mo in zip(fibers, flows, motors):
-        f.update_linear_operator(dt, eta)
+    for k, f in enumerate(fibers):
+        f.update_linear_operator(ASM_DT, ASM_ETA)
         f.update_force_operator()
-        f.update_RHS(dt, fl, mo)
-        f.apply_bc_rectangular(dt, fl, None)
+        f.update_RHS(ASM_DT, pick(flow, k), pick(f_external, k))
+        f.apply_bc_rectangular(ASM_DT, pick(flow, k), pick(bc_force, k))
         refs.append((f.A.copy(), f.RHS.copy(), f.force_operator.copy()))
+    return refs
 
-    A, RHS, F = assemble_uniform(fibers, dt, eta,
-                                 flow=np.stack(flows), f_external=np.stack(motors))
+
+def assert_assembly_matches_per_fiber_loop(fibers, **inputs):
+    from skellysim_amd.fiber_batch import assemble_uniform
+    refs = per_fiber_assembly(fibers, **inputs)
+    A, RHS, F = (t.numpy() for t in
+                 assemble_uniform(fibers, ASM_DT, ASM_ETA, **inputs))
     for k, (Ar, Rr, Fr) in enumerate(refs):
         assert np.allclose(A[k], Ar, atol=1e-13, rtol=1e-13), k
         assert np.allclose(RHS[k], Rr, atol=1e-13, rtol=1e-13), k
         assert np.allclose(F[k], Fr, atol=1e-13, rtol=1e-13), k
 
-    # with external bc forces (the f_on_fiber leg of apply_bc_rectangular)
-    bc_f = [rng.uniform(-1, 1, (3, n)) for _ in fibers]
-    refs2 = []
-    for f, fl, mo, bf in zip(fibers, flows, motors, bc_f):
-        f.update_linear_operator(dt, eta)
-        f.update_RHS(dt, fl, mo)
-        f.apply_bc_rectangular(dt, fl, bf)
-        refs2.append(f.RHS.copy())
-    _, RHS2, _ = assemble_uniform(fibers, dt, eta, flow=np.stack(flows),
-                                  f_external=np.stack(motors),
-                                  bc_force=np.stack(bc_f))
-    for k, Rr in enumerate(refs2):
-        assert np.allclose(RHS2[k], Rr, atol=1e-13, rtol=1e-13), k
 
-
-def test_torch_assembly_matches_numpy():
-    """fiber_batch.assemble_uniform_t (the on-device per-timestep assembly)
-    must equal the numpy assembly to fp64 roundoff, across mixed BCs and all
-    optional force inputs."""
-    from skellysim_amd.fiber_batch import assemble_uniform, assemble_uniform_t
+def test_batched_assembly_matches_per_fiber_loop():
+    """fiber_batch.assemble_uniform must reproduce the per-fiber
+    update_linear_operator/update_RHS/apply_bc_rectangular/force_operator
+    results exactly, across mixed BCs."""
     rng = np.random.default_rng(12)
-    dt, eta, n = 0.05, 1.3, 24
-    fibers = []
-    for k in range(5):
-        f = straight_fiber(n=n, length=0.8 + 0.1 * k,
-                           direction=rng.uniform(-1, 1, 3),
-                           x0=rng.uniform(-1, 1, 3),
-                           minus_clamped=(k % 2 == 0))
-        f.force_scale = -0.05
-        f.update_constants(eta)
-        f.update_derivatives()
-        fibers.append(f)
-    for with_forces in (False, True):
-        flow = np.stack([rng.uniform(-1, 1, (3, n)) for _ in fibers]) \
-            if with_forces else None
-        fe = np.stack([rng.uniform(-1, 1, (3, n)) for _ in fibers]) \
-            if with_forces else None
-        bf = np.stack([rng.uniform(-1, 1, (3, n)) for _ in fibers]) \
-            if with_forces else None
-        A, R, F = assemble_uniform(fibers, dt, eta, flow=flow,
-                                   f_external=fe, bc_force=bf)
-        At, Rt, Ft = assemble_uniform_t(fibers, dt, eta, flow=flow,
-                                        f_external=fe, bc_force=bf)
-        assert np.allclose(A, At.numpy(), atol=1e-13, rtol=1e-13)
-        assert np.allclose(R, Rt.numpy(), atol=1e-12, rtol=1e-13)
-        assert np.allclose(F, Ft.numpy(), atol=1e-13, rtol=1e-13)
+    fibers = assembly_fibers(rng, [k % 2 == 0 for k in range(5)])
+    flow, motors, bc_f = assembly_inputs(rng, len(fibers))
+    assert_assembly_matches_per_fiber_loop(fibers, flow=flow, f_external=motors)
+    # with external bc forces (the f_on_fiber leg of apply_bc_rectangular)
+    assert_assembly_matches_per_fiber_loop(fibers, flow=flow, f_external=motors,
+                                           bc_force=bc_f)
+
+
+def test_batched_assembly_without_and_with_all_inputs():
+    """The same assembly with all three optional inputs absent, then all
+    present, against the per-fiber loop (not against a second batched form)."""
+    rng = np.random.default_rng(13)
+    fibers = assembly_fibers(rng, [k % 2 == 0 for k in range(5)])
+    flow, fe, bf = assembly_inputs(rng, len(fibers))
+    assert_assembly_matches_per_fiber_loop(fibers)
+    assert_assembly_matches_per_fiber_loop(fibers, flow=flow, f_external=fe,
+                                           bc_force=bf)
+
+
+@pytest.mark.parametrize("minus_clamped,plus_velocity", [
+    ([True], None),                    # no Force group at the minus end
+    ([False], None),                   # no Velocity group at either end
+    ([True, True, True], None),
+    # every minus x plus combination of Velocity/Force first conditions
+    ([True, True, False, False], [True, False, True, False]),
+], ids=["one-clamped", "one-free", "three-clamped", "four-combinations"])
+def test_batched_assembly_bc_groups(minus_clamped, plus_velocity):
+    """The populations the per-BC index groups can get wrong: a group left
+    empty, a group holding every fiber, and the Velocity plus end."""
+    rng = np.random.default_rng(31)
+    fibers = assembly_fibers(rng, minus_clamped, plus_velocity)
+    flow, fe, bf = assembly_inputs(rng, len(fibers))
+    assert_assembly_matches_per_fiber_loop(fibers)
+    assert_assembly_matches_per_fiber_loop(fibers, flow=flow, f_external=fe,
+                                           bc_force=bf)
 
 
 def test_periphery_repulsion_force():
