@@ -185,8 +185,8 @@ def assemble_uniform(fibers, dt, eta, flow=None, f_external=None,
 
 def install_operators(fibers, A, RHS, F):
     """Install assembled operators on the fibers from host arrays
-    (nf, 4n, 4n), (nf, 4n), (nf, 3n, 4n): what the host matvec and
-    preconditioner paths read."""
+    (nf, 4n, 4n), (nf, 4n), (nf, 3n, 4n): what the per-fiber methods
+    (FiberFD.matvec, the RHS) read."""
     for k, f in enumerate(fibers):
         f.adopt_operator(A[k], RHS[k])
         f.force_operator = F[k]

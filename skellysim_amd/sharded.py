@@ -107,24 +107,26 @@ class Comm:
         return allgather_rows(t, self.group).numpy().reshape(-1, *a.shape[1:])
 
     def from_root(self, a, n):
-        """Rank 0's length-n fp64 numpy vector a on every rank (a is
-        ignored on the other ranks)."""
+        """Rank 0's length-n fp64 vector a on every rank (on the other
+        ranks only a's kind and device matter); numpy array or tensor in,
+        the same kind out."""
         import torch
         if self.world == 1:
             return a
-        t = torch.from_numpy(np.array(a, float) if self.rank == 0
-                             else np.zeros(n))
+        t = a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a, float))
+        t = t.contiguous() if self.rank == 0 else t.new_zeros(n)
         self._dist().broadcast(t, src=0, group=self.group)
-        return t.numpy()
+        return t if torch.is_tensor(a) else t.numpy()
 
     def sum(self, a):
-        """Elementwise sum of a numpy array over ranks."""
+        """Elementwise sum over ranks; numpy array or tensor in, the same
+        kind out."""
         import torch
         if self.world == 1:
             return a
-        t = torch.from_numpy(np.array(a))
+        t = a.clone() if torch.is_tensor(a) else torch.from_numpy(np.array(a))
         self._dist().all_reduce(t, group=self.group)
-        return t.numpy()
+        return t if torch.is_tensor(a) else t.numpy()
 
 
 class ShardedPairEvaluator:

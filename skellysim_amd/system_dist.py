@@ -12,16 +12,15 @@ own target block. GMRES runs with distributed inner products
 The reference hard-forbids its direct evaluators under >1 rank
 (system.cpp:618-623); this module is the new multi-GPU capability.
 
-There is no second pipeline here: prep, the host and the device-resident
-matvec/preconditioner, solve and step are SystemFD's, which is written
-against a rank-local layout and a communicator (see system_fd.py). This
-module supplies the two things that make a rank's view non-trivial — the
-layout (own shell rows; body block on rank 0 only) and the live
-communicator — so at world size 1 it IS the single-rank solve. Covered by
-gloo world-2 CPU tests (tests/test_dist_system.py; the device layout runs
-there on CPU tensors with oracle-backed kernel fakes) and by a world-1 HIP
-test (test_gpu_system.py); the same code drives RCCL + HIP kernels on
-multi-GPU boxes.
+There is no second pipeline here: prep, the matvec, the preconditioner,
+solve and step are SystemFD's, which is written against a rank-local layout
+and a communicator (see system_fd.py). This module supplies the two things
+that make a rank's view non-trivial — the layout (own shell rows; body block
+on rank 0 only) and the live communicator — so at world size 1 it IS the
+single-rank solve, bodies included. Covered by gloo world-2 CPU tests
+(tests/test_dist_system.py, on CPU tensors over the oracle backend) and by
+a world-1 HIP test (test_gpu_system.py); the same code drives RCCL + HIP
+kernels on multi-GPU boxes.
 """
 
 from .sharded import Comm, shard_range
@@ -34,8 +33,7 @@ class DistributedSystemFD(SystemFD):
     Construct with this rank's OWN fibers and this rank's OWN shell row block
     (shell.A / shell.M_inv hold the (3n_local, 3N_global) row slices;
     shell.nodes/normals hold the GLOBAL shell geometry, shell_rows the
-    [row0, row1) node range owned here). Requires >= 1 fiber per rank, with
-    uniform discretization for the device-resident iteration.
+    [row0, row1) node range owned here). Requires >= 1 fiber per rank.
     """
 
     # follows the default process group; the identity without one
@@ -60,15 +58,6 @@ class DistributedSystemFD(SystemFD):
         # the body objects are replicated on every rank; their solution
         # block lives only in rank 0's vector (body_container.hpp:99)
         return self.bodies if self.comm.rank == 0 else []
-
-    def _device_mode(self, requested):
-        # bodies in the device-resident iteration are single-rank only
-        if self.bodies:
-            if requested:
-                raise NotImplementedError(
-                    "bodies run on the host matvec path (round 2)")
-            return False
-        return super()._device_mode(requested)
 
 
 def distribute_fibers(fibers, world, rank):

@@ -2,18 +2,24 @@
 around the accelerated evaluators ("host control flow; kept as
 thin harness around the accelerated evaluator for configs 4-5").
 
-Mirrors the reference solve pipeline for finite-difference fibers and a
-periphery, without bodies (src/core/system.cpp):
+Mirrors the reference solve pipeline for finite-difference fibers, a
+periphery and rigid bodies (src/core/system.cpp):
   prep_state_for_solver  (system.cpp:396-459)
   apply_matvec           (system.cpp:269-324)
   apply_preconditioner   (system.cpp:248-263)
   solve / step           (system.cpp:464-493) — backward-Euler via the
                          beta_tstep/dt terms inside the fiber operator.
 
-Pair interactions, batched LU and the shell GEMVs run through a pluggable
-backend: HipBackend (the product path — device kernels, fails loudly with
-no GPU) or any object with the same methods (tests inject the CPU oracle to
-validate the orchestration end-to-end off-GPU).
+There is one matvec and one preconditioner: torch, tensor in and tensor out,
+on the backend's device, against operators that prep leaves resident there.
+The pair kernels are reached only through the backend's methods
+(SystemFD._kernel): HipBackend is the product (HIP kernels on the GPU, fails
+loudly without one); any object with the same methods on numpy arrays and no
+device is a host backend, served on CPU tensors — the tests inject the CPU
+oracle that way and run the same pipeline off-GPU.
+Fibers are held as runs — maximal blocks of consecutive fibers with equal
+node counts, each one batch for the fiber operators — so a uniform
+population is one run and a mixed one takes the same path.
 
 The pipeline is written once, for a rank-local view of the system: the
 solution vector is [own fibers | own shell rows | body block], targets are
@@ -31,93 +37,80 @@ from .sharded import Comm
 
 
 class HipBackend:
-    """Product backend: pair kernels + batched algebra on the MI355X."""
+    """Product backend: the pair kernels on the MI355X, on the device `dev`.
+    Every method takes numpy arrays or tensors and returns the same kind:
+    resident tensors in give the tensor out with no synchronization (the
+    solve pipeline), numpy in gives numpy out (prep-time and post-processing
+    callers). Both go through _eval, the one seam to the kernels."""
 
     def __init__(self, device="cuda:0"):
         import torch
-        self.torch = torch
         self.dev = torch.device(device)
 
     def _t(self, a):
-        if self.torch.is_tensor(a):
+        import torch
+        if torch.is_tensor(a):
             return a.to(self.dev)
-        return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
 
     def _eval(self, name, arrays, *scalars, **kw):
-        """evaluator.<name>(*arrays on the device, *scalars, **kw), synchronized,
-        as numpy. The function is looked up on each call, so tests can
-        replace it in the module."""
+        """evaluator.<name>_device(*arrays on the device, *scalars, **kw):
+        the tensor, asynchronous, when the arrays are tensors; else as numpy
+        (the copy back waits for the kernel). The function is looked up on
+        each call, so tests can replace it in the module."""
+        import torch
         from . import evaluator
-        out = getattr(evaluator, name)(*[self._t(a) for a in arrays], *scalars, **kw)
-        self.torch.cuda.synchronize()
-        return out.cpu().numpy()
+        out = getattr(evaluator, name + "_device")(
+            *[self._t(a) for a in arrays], *scalars, **kw)
+        return out if torch.is_tensor(arrays[0]) else out.cpu().numpy()
 
     @staticmethod
     def _f_dl(normals, density, eta):
         """Shell/body double layer: f_dl = 2*eta*n (x) d, then stresslet/eta
         (periphery.cpp:68-74)."""
+        import torch
+        if torch.is_tensor(normals):
+            from .flows import double_layer_strength
+            return double_layer_strength(normals, density, eta)
         return 2.0 * eta * np.einsum("ni,nj->nij", normals, density).reshape(-1, 9)
 
     def stokeslet(self, r_src, f_src, r_trg, eta):
-        return self._eval("stokeslet_device", (r_src, f_src, r_trg), eta)
+        return self._eval("stokeslet", (r_src, f_src, r_trg), eta)
 
     def stresslet_normal_density(self, r_src, normals, density, r_trg, eta):
-        return self._eval("stresslet_device",
+        return self._eval("stresslet",
                           (r_src, self._f_dl(normals, density, eta), r_trg), eta)
 
     def self_stokeslet_batch(self, pts, eta):
         """(nf, n, 3) -> (nf, 3n, 3n) oseen_tensor_direct per fiber."""
-        return self._eval("oseen_tensor_batched_device", (pts,), eta=eta)
+        return self._eval("oseen_tensor_batched", (pts,), eta=eta)
 
     def rotlet(self, centers, torques, r_trg, eta):
-        return self._eval("rotlet_device", (centers, r_trg, torques), eta)
+        return self._eval("rotlet", (centers, r_trg, torques), eta)
 
     def oseen_contract(self, r_src, r_trg, density, eta):
-        return self._eval("oseen_contract_device", (r_src, r_trg, density), eta)
+        return self._eval("oseen_contract", (r_src, r_trg, density), eta)
 
     # velocity gradients: (n_trg, 3, 3), G[t, i, j] = du_i/dx_j
 
     def stokeslet_grad(self, r_src, f_src, r_trg, eta):
-        return self._eval("stokeslet_grad_device", (r_src, f_src, r_trg), eta)
+        return self._eval("stokeslet_grad", (r_src, f_src, r_trg), eta)
 
     def stresslet_normal_density_grad(self, r_src, normals, density, r_trg, eta):
         """Gradient of stresslet_normal_density's field (same f_dl)."""
-        return self._eval("stresslet_grad_device",
+        return self._eval("stresslet_grad",
                           (r_src, self._f_dl(normals, density, eta), r_trg), eta)
 
     def rotlet_grad(self, centers, torques, r_trg, eta):
-        return self._eval("rotlet_grad_device", (centers, r_trg, torques), eta)
+        return self._eval("rotlet_grad", (centers, r_trg, torques), eta)
 
     def oseen_contract_grad(self, r_src, r_trg, density, eta):
-        return self._eval("oseen_contract_grad_device", (r_src, r_trg, density), eta)
+        return self._eval("oseen_contract_grad", (r_src, r_trg, density), eta)
 
     def stresslet_times_normal(self, nodes, normals, eta):
         """Dense (3n, 3n) operator (kernels.cpp:264-287; eta-independent
         factor) — the M block of the body preconditioner."""
-        return self._eval("stresslet_times_normal_device", (nodes, normals))
-
-    def batched_lu(self, A_batch):
-        """Factor (nf, m, m); returns solve(rhs_batch (nf, m)) -> (nf, m)."""
-        from .batched import BatchedLU
-        lu = BatchedLU(self._t(A_batch))
-
-        def solve(rhs):
-            x = lu.solve(self._t(rhs))
-            self.torch.cuda.synchronize()
-            return x.cpu().numpy()
-
-        return solve
-
-    def shell_ops(self, A, M_inv):
-        At, Mt = self._t(A), self._t(M_inv)
-
-        def matvec(x):
-            return (At @ self._t(x)).cpu().numpy()
-
-        def precond(x):
-            return (Mt @ self._t(x)).cpu().numpy()
-
-        return matvec, precond
+        return self._eval("stresslet_times_normal", (nodes, normals))
 
 
 class Shell:
@@ -169,12 +162,32 @@ class SystemFD:
         self.periphery_interaction = periphery_interaction
         self.backend = backend if backend is not None else HipBackend()
         self._uniform = self._fibers_uniform()
-        # (A, F) device tensors of the last prep's batched assembly, when
-        # the backend has a device (_build_device_operators adopts them)
-        self._assembled_dev = None
-        if shell is not None:
-            self._shell_matvec, self._shell_precond = \
-                self.backend.shell_ops(shell.A, shell.M_inv)
+
+    # ---- the seam to the backend ----------------------------------------
+    @property
+    def dev(self):
+        """Where the pipeline's tensors live: the backend's device, or the
+        CPU for a host backend (numpy methods, no `dev`)."""
+        import torch
+        return getattr(self.backend, "dev", torch.device("cpu"))
+
+    def _t(self, a):
+        """numpy array or tensor -> tensor on self.dev."""
+        import torch
+        if not torch.is_tensor(a):
+            a = torch.from_numpy(np.ascontiguousarray(a))
+        return a.to(self.dev)
+
+    def _kernel(self, name, *args):
+        """backend.<name>(*args) for the pipeline: tensors on self.dev in,
+        tensor out. A backend with a device takes them as they are and does
+        not synchronize; a host backend is called with numpy views."""
+        import torch
+        fn = getattr(self.backend, name)
+        if hasattr(self.backend, "dev"):
+            return fn(*args)
+        return torch.from_numpy(fn(*[np.ascontiguousarray(a.numpy())
+                                     if torch.is_tensor(a) else a for a in args]))
 
     # ---- layout helpers -------------------------------------------------
     @property
@@ -250,30 +263,6 @@ class SystemFD:
             off += b.n_nodes
         return out
 
-    def _body_flow(self, r_trg, x_bodies, forces_torques):
-        """BodyContainer::flow_spherical (body_container.cpp:269-337):
-        double layer of the bodies' surface densities + center Stokeslet of
-        the forces + center rotlet of the torques. x_bodies: the body block
-        of a solution vector (densities per body, point-major, then U/w);
-        forces_torques: (n_bodies, 6) from link conditions (matvec) or the
-        external forces (prep)."""
-        if not self.bodies:
-            return np.zeros_like(r_trg)
-        dens_parts, off = [], 0
-        for b in self.bodies:
-            dens_parts.append(
-                x_bodies[off: off + 3 * b.n_nodes].reshape(b.n_nodes, 3))
-            off += b.solution_size
-        dens = np.concatenate(dens_parts)
-        v = self.backend.stresslet_normal_density(
-            self.body_nodes(), self.body_normals(), dens, r_trg, self.eta)
-        centers = np.stack([b.position for b in self.bodies])
-        v += self.backend.stokeslet(centers, forces_torques[:, 0:3], r_trg,
-                                    self.eta)
-        v += self.backend.rotlet(centers, forces_torques[:, 3:6], r_trg,
-                                 self.eta)
-        return v
-
     def _global_body_solution(self, x):
         """The body block of the solution-layout vector x, from the rank
         that holds it (rank 0) on every rank (system.cpp:309)."""
@@ -299,59 +288,86 @@ class SystemFD:
         """All fibers share one discretization (the batched paths apply)."""
         return all(f.n_nodes == self.fibers[0].n_nodes for f in self.fibers)
 
-    # ---- fiber container operations ------------------------------------
-    def _build_self_stokeslets(self):
-        """Materialize the per-fiber self-stokeslets that prep reset (lazy:
-        the device-resident path never needs the host copies)."""
-        if not self.fibers or self.fibers[0].stokeslet is not None:
-            return
-        if self._uniform:
-            pts = np.stack([f.x.T for f in self.fibers])
-            G = self.backend.self_stokeslet_batch(pts, self.eta)
-            for f, g in zip(self.fibers, G):
-                f.stokeslet = g
-        else:
-            # mixed discretizations: per-fiber batches of one
-            for f in self.fibers:
-                f.stokeslet = self.backend.self_stokeslet_batch(
-                    f.x.T[None], self.eta)[0]
+    def _fiber_runs(self):
+        """[i0, i1) fiber index ranges of the runs: maximal blocks of
+        consecutive fibers with equal n_nodes, each batched as one."""
+        runs = []
+        for i, f in enumerate(self.fibers):
+            if runs and self.fibers[runs[-1][0]].n_nodes == f.n_nodes:
+                runs[-1][1] = i + 1
+            else:
+                runs.append([i, i + 1])
+        return runs
 
-    def _fiber_flow(self, r_trg, fib_forces):
-        """FiberContainerFiniteDifference::flow (f_c_fd.cpp:172-214):
-        quadrature-weighted stokeslet of fiber forces at r_trg, minus the
-        per-fiber self term on the fiber's own slice of the targets. The
-        sources are ALL ranks' fibers (positions and weighted forces
-        gathered — the reference's per-apply MPI_Allgatherv); the self
-        term is this rank's fibers against their own wf, and their nodes
-        lead r_trg."""
-        if self.fibers:
-            w = np.concatenate([f.quadrature_weights() for f in self.fibers])
-            wf = fib_forces * w[:, None]
-        else:
-            wf = np.zeros((0, 3))
-        r_src = self.comm.gather_rows(self.fiber_nodes())
-        if not len(r_src):
-            return np.zeros_like(r_trg)
-        vel = self.backend.stokeslet(r_src, self.comm.gather_rows(wf), r_trg,
-                                     self.eta)
-        self._build_self_stokeslets()
-        for f, a, b in self._fiber_node_slices():
-            # stokeslet_ and wf are point-major interleaved (xyz per node),
-            # matching the reference's VectorMap flattening (f_c_fd.cpp:204-208)
-            vel[a:b] -= (f.stokeslet @ wf[a:b].reshape(-1)).reshape(f.n_nodes, 3)
+    # ---- resident state and the flow stages -----------------------------
+    def _build_geometry(self):
+        """Start the resident state self._ops with what the flow stages
+        need. It depends on positions and eta only, so prep builds it first
+        and runs its own flows through the same stages as the matvec."""
+        T = self._t
+        d = self._ops = dict(runs=[])
+        a = na = 0
+        for i0, i1 in self._fiber_runs():
+            fibs = self.fibers[i0:i1]
+            nf, n = len(fibs), fibs[0].n_nodes
+            d["runs"].append(dict(
+                fibers=fibs, nf=nf, n=n,
+                sol=slice(a, a + 4 * nf * n), nodes=slice(na, na + nf * n),
+                # self-stokeslets built directly on device (kernels.cpp:146-195)
+                G=self._kernel("self_stokeslet_batch",
+                               T(np.stack([f.x.T for f in fibs])), self.eta),
+                w=T(np.concatenate([f.quadrature_weights() for f in fibs]))))
+            a, na = a + 4 * nf * n, na + nf * n
+        d["fib_size"], d["fib_nodes"], d["sh_size"] = a, na, self.shell_sol_size
+        d["r_fib"] = T(self.fiber_nodes())
+        # the one solve-static gather: fiber source positions of all ranks
+        d["r_fib_all"] = self.comm.gather_rows(d["r_fib"])
+        d["r_all"] = T(self.all_nodes())
+        if self.shell:
+            d["sh_nodes"] = T(self.shell.nodes)
+            d["sh_normals"] = T(self.shell.normals)
+        if self.bodies:
+            d["body_nodes"] = T(self.body_nodes())
+            d["body_normals"] = T(self.body_normals())
+            d["centers"] = T(np.stack([b.position for b in self.bodies]))
+
+    def _fiber_flow(self, forces):
+        """FiberContainerFiniteDifference::flow (f_c_fd.cpp:172-214) at the
+        local nodes: quadrature-weighted stokeslet of the fiber forces,
+        minus the per-fiber self term on the fiber's own nodes. forces: per
+        run, (nf*n, 3) node-major. The sources are ALL ranks' fibers (the
+        weighted forces gathered per apply — the reference's
+        MPI_Allgatherv); the self term is this rank's fibers against their
+        own wf, and their nodes lead the targets."""
+        import torch
+        d = self._ops
+        if not len(d["r_fib_all"]):
+            return torch.zeros_like(d["r_all"])
+        wf = [f * r["w"][:, None] for f, r in zip(forces, d["runs"])]
+        wf_all = wf[0] if len(wf) == 1 else torch.cat(wf)
+        vel = self._kernel("stokeslet", d["r_fib_all"],
+                           self.comm.gather_rows(wf_all), d["r_all"], self.eta)
+        for r, wf_r in zip(d["runs"], wf):
+            # G and wf are point-major interleaved (xyz per node), matching
+            # the reference's VectorMap flattening (f_c_fd.cpp:203-210)
+            vel[r["nodes"]] -= torch.bmm(
+                r["G"], wf_r.reshape(r["nf"], 3 * r["n"], 1)).reshape(-1, 3)
         return vel
 
-    def _apply_fiber_force(self, x_fib):
-        """force_operator per fiber -> (n_fib_nodes, 3) (f_c_fd.cpp:272-287)."""
-        fw = np.zeros((self.fiber_node_count, 3))
-        node_off = 0
-        for f, a, b in self._fiber_slices():
-            ff = f.force_operator @ x_fib[a:b]
-            np_ = f.n_nodes
-            for i in range(3):
-                fw[node_off: node_off + np_, i] = ff[i * np_: (i + 1) * np_]
-            node_off += np_
-        return fw
+    def _body_flow(self, densities, forces_torques):
+        """BodyContainer::flow_spherical (body_container.cpp:269-337) at the
+        local nodes: double layer of ALL bodies' surface densities (n, 3) +
+        center Stokeslet of the forces + center rotlet of the torques.
+        forces_torques: (n_bodies, 6) from the link conditions (matvec) or
+        the external forces (prep)."""
+        d, eta, kernel = self._ops, self.eta, self._kernel
+        v = kernel("stresslet_normal_density", d["body_nodes"],
+                   d["body_normals"], densities, d["r_all"], eta)
+        v += kernel("stokeslet", d["centers"],
+                    forces_torques[:, 0:3].contiguous(), d["r_all"], eta)
+        v += kernel("rotlet", d["centers"],
+                    forces_torques[:, 3:6].contiguous(), d["r_all"], eta)
+        return v
 
     # ---- solver pipeline ------------------------------------------------
     def prep_state_for_solver(self):
@@ -377,11 +393,10 @@ class SystemFD:
                 f.update_linear_operator(dt, eta)
                 f.update_force_operator()
 
-        # self-stokeslets (fiber_finite_difference.cpp:56) are built lazily:
-        # the device-resident solve path builds its own resident stack, and
-        # the host path materializes them on first _fiber_flow use
-        for f in self.fibers:
-            f.stokeslet = None
+        # positions, self-stokeslets (fiber_finite_difference.cpp:56) and
+        # quadrature weights, resident for the flows below and in the matvec
+        self._build_geometry()
+        T = self._t
 
         r_all = self.all_nodes()
         nf_nodes = self.fiber_node_count
@@ -411,7 +426,9 @@ class SystemFD:
         v_all = np.zeros_like(r_all)
         if nf_nodes and (self.periphery_interaction is not None
                          or self.steric_interaction is not None):
-            v_all += self._fiber_flow(r_all, ext)
+            ext_t = T(ext)
+            v_all += self._fiber_flow(
+                [ext_t[r["nodes"]] for r in self._ops["runs"]]).cpu().numpy()
         if self.background_flow is not None:
             v_all += self.background_flow(r_all)
         # point + background sources (psc_.flow / bs_.flow, system.cpp:445-446)
@@ -430,14 +447,15 @@ class SystemFD:
                                                b.external_torque])
                                for b in self.bodies])
             if np.any(ext_ft):
-                # global-sized zero densities: the flow's sources are all
-                # the bodies, whichever rank holds their solution block
+                # zero densities on every body's nodes: the flow's sources
+                # are all the bodies, whichever rank holds their block
                 v_all += self._body_flow(
-                    r_all, np.zeros(self.global_body_sol_size), ext_ft)
+                    T(np.zeros((self.body_node_count, 3))),
+                    T(ext_ft)).cpu().numpy()
 
         motor = motor + ext  # total_force_fibers (system.cpp:450)
         v_fib = v_all[:nf_nodes]
-        self._assembled_dev = None
+        assembled = None
         if self._uniform and self.fibers:
             # batched assembly (operator + RHS + BCs + force operator) —
             # numerically identical to the per-fiber loop (fiber_batch.py)
@@ -448,18 +466,15 @@ class SystemFD:
             motor_b = motor.reshape(nf, n, 3).transpose(0, 2, 1)
             ext_b = ext.reshape(nf, n, 3).transpose(0, 2, 1) \
                 if self.periphery_interaction is not None else None
-            # assemble on the backend's device when it has one (the
-            # dominant prep cost); materialize host copies so the host
-            # matvec/precond paths stay valid, and keep the resident
-            # tensors for _build_device_operators
-            dev = getattr(self.backend, "dev", None)
+            # assemble on the backend's device (the dominant prep cost) and
+            # keep the resident tensors for _build_operators; the fibers
+            # get host copies, as from the per-fiber methods
             A_t, RHS_t, F_t = assemble_uniform(
                 self.fibers, dt, eta, flow=flow_b, f_external=motor_b,
-                bc_force=ext_b, device=dev)
+                bc_force=ext_b, device=self.dev)
             install_operators(self.fibers, A_t.cpu().numpy(),
                               RHS_t.cpu().numpy(), F_t.cpu().numpy())
-            if dev is not None:
-                self._assembled_dev = (A_t, F_t)
+            assembled = (A_t, F_t)
         else:
             for f, a, b in self._fiber_node_slices():
                 f.update_RHS(dt, v_fib[a:b].T, motor[a:b].T)
@@ -467,11 +482,7 @@ class SystemFD:
                                        if self.periphery_interaction is not None
                                        else None)
 
-        # preconditioner: batched LU of the (BC-applied) fiber operators,
-        # factored on first apply_preconditioner use (lazy — the
-        # device-resident solve path factors its own resident copy in
-        # _build_device_operators)
-        self._fiber_lu_solves = None
+        self._build_operators(assembled)
 
         rhs_parts = [f.RHS for f in self.fibers]
         sh_nodes = self.shell_sol_size // 3
@@ -483,374 +494,233 @@ class SystemFD:
         self.RHS = np.concatenate(rhs_parts) if rhs_parts else np.zeros(0)
         return self.RHS
 
-    def apply_matvec(self, x):
-        """system.cpp:269-324 (fibers + shell + bodies): all ranks' sources,
-        this rank's targets and rows."""
-        nf_nodes = self.fiber_node_count
-        sh_nodes = self.shell_sol_size // 3
-        x_fib = x[: self.fiber_sol_size]
-        x_shell = x[self.fiber_sol_size: self.fiber_sol_size + self.shell_sol_size]
-        r_all = self.all_nodes()
+    def _build_operators(self, assembled=None):
+        """Complete self._ops with the operators of the assembled state, so
+        a whole GMRES iteration (matvec + preconditioner) runs on the
+        backend's device with no host traffic. assembled: the (A, F)
+        tensors of a uniform population's batched assembly, adopted as its
+        one run; otherwise each run stacks its fibers' operators."""
+        import torch
+        from .batched import BatchedLU
+        T, dev = self._t, self.dev
+        d = self._ops
+        for r in d["runs"]:
+            fibs, m = r["fibers"], r["fibers"][0].mats
+            r["A"], r["F"] = assembled if assembled is not None else (
+                T(np.stack([f.A for f in fibs])),
+                T(np.stack([f.force_operator for f in fibs])))
+            r["lu"] = BatchedLU(r["A"])
+            r["xs"] = T(np.stack([f.xs for f in fibs]))              # (nf, 3, n)
+            # the tension row's D_1 is D_1_0 * 2/length_prev, each fiber's
+            # own (fiber_fd.matvec); the factor rides on a copy of xs
+            r["xs_D1"] = r["xs"] * T(np.array(
+                [2.0 / f.length_prev for f in fibs]))[:, None, None]
+            r["D1T"] = T(m["D_1_0"].T)
+            r["P_ds"] = T(m["P_downsample_bc"])                      # (4n-14, 4n)
+            r["plus_vel"] = T(np.array(
+                [1.0 if f.bc_plus[0] == "Velocity" else 0.0 for f in fibs]))
+            # fiber<->body link statics (body.py) of the attached fibers
+            att = [i for i, f in enumerate(fibs) if f.binding_site[0] >= 0] \
+                if self.bodies else []
+            r["att"] = None
+            if att:
+                fa = [fibs[i] for i in att]
+                site = np.stack(
+                    [self.bodies[ib].nucleation_sites[js] - self.bodies[ib].position
+                     for ib, js in (f.binding_site for f in fa)])
+                col = lambda vals: T(np.array(vals))[:, None]
+                r["att"] = dict(
+                    idx=torch.tensor(att, dtype=torch.long, device=dev),
+                    body=torch.tensor([f.binding_site[0] for f in fa],
+                                      dtype=torch.long, device=dev),
+                    site=T(site),
+                    site_hat=T(site / np.linalg.norm(site, axis=1, keepdims=True)),
+                    xs0=T(np.stack([f.xs[:, 0] for f in fa])),
+                    d2c0=T(m["D_2_0"][:, 0]), d3c0=T(m["D_3_0"][:, 0]),
+                    E=col([f.bending_rigidity for f in fa]),
+                    s2=col([(2.0 / f.length) ** 2 for f in fa]),
+                    s3=col([(2.0 / f.length) ** 3 for f in fa]))
+        if self.shell:
+            # transposed copies: rocBLAS dgemv's reduction (trans) path is
+            # ~1.5x the axpy path on these square operators (measured
+            # 0.96 vs 1.43 ms at 24576^2, tools/prof_iter.py), so store
+            # X^T contiguous and apply as mv(X_T.t(), v). HBM cost is one
+            # extra copy of each operator — trivial in 288 GB. A rank's
+            # (3n_local, 3N) row block takes the same form. Kept on the
+            # shell, per device, across preps.
+            cache = self.shell.__dict__.setdefault("_transposed", {})
+            if dev not in cache:
+                cache[dev] = tuple(T(X).t().contiguous()
+                                   for X in (self.shell.A, self.shell.M_inv))
+            d["sh_A_T"], d["sh_Minv_T"] = cache[dev]
+        if self.bodies:
+            # [densities | U, w] offsets of every body in the global block
+            d["body_offsets"] = np.cumsum(
+                [0] + [b.solution_size for b in self.bodies])[:-1].tolist()
+            # BatchedLU(batch of 1) so the per-iteration solves take the
+            # trsm path — magma's lu_solve corrupts under deep stream
+            # queues (profiles/cadence_matrix_r02.md) and the
+            # preconditioner runs at sync cadence 8 by default
+            d["bodies"] = [dict(n=b.n_nodes, e=T(np.stack(b.e_sub)),  # (3, n, 3)
+                                w=T(b.weights), K=T(b.K),
+                                lu=BatchedLU(T(b._A_dense)[None]))
+                           for b in self._own_bodies()]
 
-        fw = self._apply_fiber_force(x_fib)
-        v_all = self._fiber_flow(r_all, fw)
+    def _link_conditions(self, r, x_run, body_vels, body_ft):
+        """Fiber<->body link conditions of one run's attached fibers
+        (body_container.cpp:171-268; body.calculate_link_conditions is the
+        per-fiber statement). Adds the force and torque they exert on their
+        bodies into body_ft (n_bodies, 6); returns the run's (nf, 7)
+        v_boundary rows, zero for unattached fibers."""
+        import torch
+        at, n = r["att"], r["n"]
+        xa = x_run[at["idx"]]
+        x_new = xa[:, : 3 * n].reshape(-1, 3, n)
+        T0 = xa[:, 3 * n, None]
+        xss0 = torch.einsum("ain,n->ai", x_new, at["d2c0"]) * at["s2"]
+        xsss0 = torch.einsum("ain,n->ai", x_new, at["d3c0"]) * at["s3"]
+        xs0, E, site = at["xs0"], at["E"], at["site"]
+        F_b = -E * xsss0 + xs0 * T0
+        L_b = (-E * torch.cross(site, xsss0, dim=1)
+               + torch.cross(site, xs0, dim=1) * T0
+               + E * torch.cross(xs0, xss0, dim=1))
+        body_ft.index_add_(0, at["body"], torch.cat([F_b, L_b], dim=1))
+        U_att = body_vels[at["body"], 0:3]
+        w_att = body_vels[at["body"], 3:6]
+        v_f = -U_att - torch.cross(w_att, site, dim=1)
+        tc = -(xs0 * U_att).sum(dim=1) \
+            + (torch.cross(xs0, site, dim=1) * w_att).sum(dim=1)
+        w_f = torch.cross(at["site_hat"], w_att, dim=1)
+        vel7 = x_run.new_zeros((r["nf"], 7))
+        vel7[at["idx"]] = torch.cat([v_f, tc[:, None], w_f], dim=1)
+        return vel7
+
+    def apply_matvec(self, x):
+        """system.cpp:269-324 (fibers + shell + bodies), x and the result
+        fp64 tensors on the backend's device in the solution layout: all
+        ranks' sources, this rank's targets (node order [fib | shell |
+        body]) and rows. Per apply, wf and the shell density are gathered
+        (RCCL over xGMI on GPUs), the body block is taken from rank 0 and
+        the link forces are summed."""
+        import torch
+        d, eta, kernel = self._ops, self.eta, self._kernel
+        runs = d["runs"]
+        nf_nodes = d["fib_nodes"]  # LOCAL fiber nodes (targets)
+        sh = slice(d["fib_size"], d["fib_size"] + d["sh_size"])
+        body_node0 = nf_nodes + d["sh_size"] // 3
+        x_runs = [x[r["sol"]].reshape(r["nf"], 4 * r["n"]) for r in runs]
+
+        # forces: F @ x (component-major) -> node-major (nf*n, 3)
+        v_all = self._fiber_flow(
+            [torch.bmm(r["F"], xr.unsqueeze(-1)).reshape(r["nf"], 3, r["n"])
+             .permute(0, 2, 1).reshape(-1, 3) for r, xr in zip(runs, x_runs)])
 
         if self.shell:
             # the GLOBAL density (periphery.cpp:26,44 Allgatherv); its
             # double layer flows to fibers AND bodies, not to the shell
             # itself (system.cpp:302-305,314-316)
-            dens = self.comm.gather_rows(x_shell.reshape(-1, 3))
-            trg = np.concatenate([r_all[:nf_nodes],
-                                  r_all[nf_nodes + sh_nodes:]])
-            if len(trg):
-                v = self.backend.stresslet_normal_density(
-                    self.shell.nodes, self.shell.normals, dens, trg, self.eta)
-                v_all[:nf_nodes] += v[:nf_nodes]
-                v_all[nf_nodes + sh_nodes:] += v[nf_nodes:]
+            dens = self.comm.gather_rows(x[sh].reshape(-1, 3))
+            if nf_nodes:
+                v_all[:nf_nodes] += kernel(
+                    "stresslet_normal_density", d["sh_nodes"], d["sh_normals"],
+                    dens, d["r_fib"], eta)
+            if self._own_bodies():
+                v_all[body_node0:] += kernel(
+                    "stresslet_normal_density", d["sh_nodes"], d["sh_normals"],
+                    dens, d["body_nodes"], eta)
 
-        vel_on_fiber = None
+        vel7 = [None] * len(runs)
         if self.bodies:
-            # fiber<->body link conditions + body flow (system.cpp:308-317).
             # Bodies follow the reference's ownership model: the geometry
             # is replicated on every rank, the solution block lives in
             # rank 0's vector and is broadcast per apply
             # (body_container.hpp:99, system.cpp:309), and the link forces
             # each rank computes from its own fibers are summed
             # (body_container.cpp:131)
-            from .body import calculate_link_conditions
             x_bodies = self._global_body_solution(x)
-            body_vels, off = [], 0
-            for b in self.bodies:
-                body_vels.append(x_bodies[off + 3 * b.n_nodes:
-                                          off + b.solution_size])
-                off += b.solution_size
-            vel_on_fiber, body_ft = calculate_link_conditions(
-                self.fibers, x_fib, np.stack(body_vels), self.bodies)
-            v_all += self._body_flow(r_all, x_bodies,
-                                     self.comm.sum(body_ft))
+            dens_b = torch.cat([x_bodies[o: o + 3 * b.n_nodes].reshape(-1, 3)
+                                for o, b in zip(d["body_offsets"], self.bodies)])
+            body_vels = torch.stack([x_bodies[o + 3 * b.n_nodes: o + b.solution_size]
+                                     for o, b in zip(d["body_offsets"], self.bodies)])
+            body_ft = torch.zeros_like(body_vels)
+            for k, (r, xr) in enumerate(zip(runs, x_runs)):
+                if r["att"] is not None:
+                    vel7[k] = self._link_conditions(r, xr, body_vels, body_ft)
+            v_all += self._body_flow(dens_b, self.comm.sum(body_ft))
 
-        res = np.zeros_like(x)
-        v_fib = v_all[:nf_nodes]
-        for i, ((f, a, b), (_, na, nb)) in enumerate(
-                zip(self._fiber_slices(), self._fiber_node_slices())):
-            vb = vel_on_fiber[i] if vel_on_fiber is not None else None
-            res[a:b] = f.matvec(x_fib[a:b], v_fib[na:nb].T, vb)
+        res = torch.empty_like(x)
+        for r, xr, v7 in zip(runs, x_runs, vel7):
+            res[r["sol"]] = self._fiber_block(r, xr, v_all[r["nodes"]],
+                                              v7).reshape(-1)
         if self.shell:
             # own rows of the dense operator against the global density
             # (row-distributed dense ops, periphery.cpp:34-47)
-            v_shell = v_all[nf_nodes: nf_nodes + sh_nodes]
-            res[self.fiber_sol_size: self.fiber_sol_size + self.shell_sol_size] = \
-                self._shell_matvec(dens.reshape(-1)) + v_shell.reshape(-1)
-        for (b, a, bb), (_, na, nb) in zip(self._body_sol_slices(),
-                                           self._body_node_slices()):
-            res[a:bb] = b.matvec(v_all[na:nb], x[a:bb])
+            v_shell = v_all[nf_nodes: body_node0].reshape(-1)
+            res[sh] = torch.addmv(v_shell, d["sh_A_T"].t(), dens.reshape(-1))
+        off, node = sh.stop, body_node0
+        for bd in d.get("bodies", ()):
+            # body_spherical.cpp:39-62 (body.SphericalBody.matvec)
+            nn = bd["n"]
+            xb = x[off: off + 3 * nn + 6]
+            dloc, U = xb[: 3 * nn].reshape(nn, 3), xb[3 * nn:]
+            sub = (dloc[:, 0:1] * bd["e"][0] + dloc[:, 1:2] * bd["e"][1]
+                   + dloc[:, 2:3] * bd["e"][2]) / bd["w"][:, None]
+            res[off: off + 3 * nn] = \
+                (-sub + v_all[node: node + nn]).reshape(-1) - bd["K"] @ U
+            res[off + 3 * nn: off + 3 * nn + 6] = -bd["K"].T @ xb[: 3 * nn] + U
+            off, node = off + 3 * nn + 6, node + nn
         return res
 
-    def apply_preconditioner(self, x):
-        """system.cpp:248-263."""
-        res = np.zeros_like(x)
-        # one batched LU over all fibers when they share a discretization,
-        # otherwise per-fiber batches of one
-        batches = [self.fibers] if self._uniform and self.fibers \
-            else [[f] for f in self.fibers]
-        if self._fiber_lu_solves is None:
-            self._fiber_lu_solves = [
-                self.backend.batched_lu(np.stack([f.A for f in fibs]))
-                for fibs in batches]
-        off = 0
-        for fibs, solve in zip(batches, self._fiber_lu_solves):
-            m = 4 * fibs[0].n_nodes
-            end = off + len(fibs) * m
-            res[off:end] = solve(x[off:end].reshape(len(fibs), m)).reshape(-1)
-            off = end
-        if self.shell:
-            # own rows of M_inv against the global shell vector
-            sh = slice(self.fiber_sol_size,
-                       self.fiber_sol_size + self.shell_sol_size)
-            res[sh] = self._shell_precond(
-                self.comm.gather_rows(x[sh].reshape(-1, 3)).reshape(-1))
-        for b, a, bb in self._body_sol_slices():
-            res[a:bb] = b.apply_preconditioner(x[a:bb])
-        return res
-
-    # ---- device-resident iteration (uniform fibers + HipBackend) --------
-    def _build_device_operators(self):
-        """Stack the per-fiber operators in HBM so the entire GMRES iteration
-        (matvec + preconditioner) runs on device with zero host traffic —
-        SURVEY.md §8f row 3 in full."""
-        import torch
-        dev = self.backend.dev
-        T = self.backend._t
-
-        nf = len(self.fibers)
-        f0 = self.fibers[0]
-        n = f0.n_nodes
-        self._dev = dict(nf=nf, n=n)
-        d = self._dev
-        if self._assembled_dev is not None:
-            d["A"], d["F"] = self._assembled_dev  # already resident from prep
-        else:
-            d["A"] = T(np.stack([f.A for f in self.fibers]))
-            d["F"] = T(np.stack([f.force_operator for f in self.fibers]))
-        # self-stokeslets built directly on device (kernels.cpp:146-195)
-        from .evaluator import oseen_tensor_batched_device
-        pts = T(np.stack([f.x.T for f in self.fibers]))
-        d["G"] = oseen_tensor_batched_device(pts, eta=self.eta)
-        d["xs"] = T(np.stack([f.xs for f in self.fibers]))          # (nf, 3, n)
-        d["w"] = T(np.concatenate([f.quadrature_weights() for f in self.fibers]))
-        d["P_ds"] = T(f0.mats["P_downsample_bc"])                    # (4n-14, 4n)
-        d["D1preT"] = T((f0.mats["D_1_0"] * (2.0 / f0.length_prev)).T)
-        d["r_fib"] = T(self.fiber_nodes())
-        # the one solve-static gather: fiber source positions of all ranks
-        d["r_fib_all"] = self.comm.gather_rows(d["r_fib"])
-        d["r_all"] = T(self.all_nodes())
-        d["plus_vel"] = T(np.array(
-            [1.0 if f.bc_plus[0] == "Velocity" else 0.0 for f in self.fibers]))
-        if self.shell:
-            d["sh_nodes"] = T(self.shell.nodes)
-            d["sh_normals"] = T(self.shell.normals)
-            d["sh_A"] = self.shell.A if torch.is_tensor(self.shell.A) \
-                else T(self.shell.A)
-            d["sh_Minv"] = self.shell.M_inv if torch.is_tensor(self.shell.M_inv) \
-                else T(self.shell.M_inv)
-            # transposed copies: rocBLAS dgemv's reduction (trans) path is
-            # ~1.5x the axpy path on these square operators (measured
-            # 0.96 vs 1.43 ms at 24576^2, tools/prof_iter.py), so store
-            # X^T contiguous and apply as mv(X_T.t(), v). HBM cost is one
-            # extra copy of each operator — trivial in 288 GB. A rank's
-            # (3n_local, 3N) row block takes the same form.
-            if getattr(self.shell, "_A_T", None) is None:
-                self.shell._A_T = d["sh_A"].t().contiguous()
-                self.shell._Minv_T = d["sh_Minv"].t().contiguous()
-            d["sh_A_T"] = self.shell._A_T
-            d["sh_Minv_T"] = self.shell._Minv_T
-        from .batched import BatchedLU
-        d["lu"] = BatchedLU(d["A"])
-
-        if self.bodies:
-            # per-body blocks + fiber<->body link statics (body.py)
-            blocks = []
-            from .batched import BatchedLU
-            for b in self.bodies:
-                # BatchedLU(batch of 1) so the per-iteration solves take the
-                # trsm path — magma's lu_solve corrupts under deep stream
-                # queues (profiles/cadence_matrix_r02.md) and the device
-                # preconditioner runs at sync cadence 8 by default
-                blocks.append(dict(n=b.n_nodes,
-                                   e=T(np.stack(b.e_sub)),     # (3, n, 3)
-                                   w=T(b.weights), K=T(b.K),
-                                   lu=BatchedLU(T(b._A_dense)[None])))
-            d["bodies"] = blocks
-            d["body_nodes"] = T(self.body_nodes())
-            d["body_normals"] = T(self.body_normals())
-            d["centers"] = T(np.stack([b.position for b in self.bodies]))
-            att = [(i, f.binding_site) for i, f in enumerate(self.fibers)
-                   if f.binding_site[0] >= 0]
-            d["att_idx"] = torch.tensor([i for i, _ in att], dtype=torch.long,
-                                        device=dev)
-            d["att_body"] = torch.tensor([bs[0] for _, bs in att],
-                                         dtype=torch.long, device=dev)
-            site = np.stack([self.bodies[bs[0]].nucleation_sites[bs[1]]
-                             - self.bodies[bs[0]].position
-                             for _, bs in att]) if att else np.zeros((0, 3))
-            d["att_site"] = T(site)
-            d["att_site_hat"] = T(site / np.linalg.norm(site, axis=1,
-                                                        keepdims=True)) \
-                if len(att) else T(site)
-            d["d2c0"] = T(f0.mats["D_2_0"][:, 0])
-            d["d3c0"] = T(f0.mats["D_3_0"][:, 0])
-            d["E_fib"] = T(np.array([f.bending_rigidity for f in self.fibers]))
-            d["s2"] = T(np.array([(2.0 / f.length) ** 2 for f in self.fibers]))
-            d["s3"] = T(np.array([(2.0 / f.length) ** 3 for f in self.fibers]))
-
-    def _apply_matvec_device(self, x):
-        """apply_matvec entirely on device (torch fp64 CUDA vector in/out);
-        covers fibers + shell + bodies (node order [fib | shell | body],
-        system.cpp:269-324). The collectives are apply_matvec's: wf and
-        the shell density are gathered once per apply (RCCL over xGMI on
-        GPUs), the fiber positions once per build; bodies here are
-        single-rank only."""
-        import torch
-        from .evaluator import stokeslet_device, stresslet_device
-        from .flows import double_layer_strength
-        d = self._dev
-        nf, n = d["nf"], d["n"]
-        eta = self.eta
-        nf_nodes = nf * n  # LOCAL fiber nodes (targets); sources are global
-        sh_size = self.shell_sol_size
-        sh_nodes_n = sh_size // 3
-        x_fib = x[: 4 * nf_nodes].reshape(nf, 4 * n)
-        x_shell = x[4 * nf_nodes: 4 * nf_nodes + sh_size]
-        x_bodies = x[4 * nf_nodes + sh_size:]
-
-        # forces: F @ x (component-major) -> node-major (nf*n, 3)
-        fw = torch.bmm(d["F"], x_fib.unsqueeze(-1)).squeeze(-1)     # (nf, 3n)
-        fw_nodes = fw.reshape(nf, 3, n).permute(0, 2, 1).reshape(nf_nodes, 3)
-        wf = (fw_nodes * d["w"][:, None]).contiguous()
-
-        v_all = stokeslet_device(d["r_fib_all"], self.comm.gather_rows(wf),
-                                 d["r_all"], eta)
-        # per-fiber self subtraction, on the OWN fibers' wf only
-        # (point-major, f_c_fd.cpp:203-210)
-        wf_pm = wf.reshape(nf, 3 * n, 1)
-        corr = torch.bmm(d["G"], wf_pm).reshape(nf_nodes, 3)
-        v_all[:nf_nodes] -= corr
-
-        if self.shell:
-            # shell double layer (of the global density) flows to fibers
-            # and bodies, not to itself
-            dens = self.comm.gather_rows(x_shell.reshape(-1, 3))
-            f_dl = double_layer_strength(d["sh_normals"], dens, eta)
-            v_all[:nf_nodes] += stresslet_device(d["sh_nodes"], f_dl,
-                                                 d["r_fib"], eta)
-            if self.bodies:
-                v_all[nf_nodes + sh_nodes_n:] += stresslet_device(
-                    d["sh_nodes"], f_dl, d["body_nodes"], eta)
-
-        vel7 = None
-        if self.bodies:
-            from .evaluator import rotlet_device
-            nb = len(self.bodies)
-            # per-body [U, w] slices of the body block
-            body_vels = torch.zeros((nb, 6), dtype=x.dtype, device=x.device)
-            dens_parts, off = [], 0
-            for bi, bd in enumerate(d["bodies"]):
-                nn = bd["n"]
-                dens_parts.append(x_bodies[off: off + 3 * nn].reshape(nn, 3))
-                body_vels[bi] = x_bodies[off + 3 * nn: off + 3 * nn + 6]
-                off += 3 * nn + 6
-            bdens = torch.cat(dens_parts)
-
-            # link conditions (body_container.cpp:171-268) in torch
-            body_ft = torch.zeros((nb, 6), dtype=x.dtype, device=x.device)
-            ai = d["att_idx"]
-            if len(ai):
-                xa = x_fib[ai]
-                x_new = xa[:, : 3 * n].reshape(-1, 3, n)
-                T0 = xa[:, 3 * n]
-                xss0 = torch.einsum("ain,n->ai", x_new, d["d2c0"]) \
-                    * d["s2"][ai][:, None]
-                xsss0 = torch.einsum("ain,n->ai", x_new, d["d3c0"]) \
-                    * d["s3"][ai][:, None]
-                xs0 = d["xs"][ai][:, :, 0]
-                E = d["E_fib"][ai][:, None]
-                site = d["att_site"]
-                F_b = -E * xsss0 + xs0 * T0[:, None]
-                L_b = (-E * torch.cross(site, xsss0, dim=1)
-                       + torch.cross(site, xs0, dim=1) * T0[:, None]
-                       + E * torch.cross(xs0, xss0, dim=1))
-                body_ft.index_add_(0, d["att_body"],
-                                   torch.cat([F_b, L_b], dim=1))
-                U_att = body_vels[d["att_body"], 0:3]
-                w_att = body_vels[d["att_body"], 3:6]
-                v_f = -U_att - torch.cross(w_att, site, dim=1)
-                tc = -(xs0 * U_att).sum(dim=1) \
-                    + (torch.cross(xs0, site, dim=1) * w_att).sum(dim=1)
-                w_f = torch.cross(d["att_site_hat"], w_att, dim=1)
-                vel7 = torch.zeros((nf, 7), dtype=x.dtype, device=x.device)
-                vel7[ai] = torch.cat([v_f, tc[:, None], w_f], dim=1)
-
-            # body flow: double layer + center stokeslet/rotlet of link F/T
-            f_dl_b = double_layer_strength(d["body_normals"], bdens, eta)
-            v_all += stresslet_device(d["body_nodes"], f_dl_b, d["r_all"], eta)
-            v_all += stokeslet_device(d["centers"],
-                                      body_ft[:, 0:3].contiguous(),
-                                      d["r_all"], eta)
-            v_all += rotlet_device(d["centers"], d["r_all"],
-                                   body_ft[:, 3:6].contiguous(), eta)
-
-        res = torch.empty_like(x)
-        res[: 4 * nf_nodes] = self._fiber_block_device(
-            x_fib, v_all[:nf_nodes], vel7).reshape(-1)
-        if self.shell:
-            # own rows against the global density (periphery.cpp:34-47)
-            v_shell = v_all[nf_nodes: nf_nodes + sh_nodes_n].reshape(-1)
-            res[4 * nf_nodes: 4 * nf_nodes + sh_size] = \
-                torch.addmv(v_shell, d["sh_A_T"].t(), dens.reshape(-1))
-        if self.bodies:
-            off = 0
-            off_node = nf_nodes + sh_nodes_n
-            base = 4 * nf_nodes + sh_size
-            for bd in d["bodies"]:
-                nn = bd["n"]
-                xb = x_bodies[off: off + 3 * nn + 6]
-                dloc = xb[: 3 * nn].reshape(nn, 3)
-                U = xb[3 * nn:]
-                sub = (dloc[:, 0:1] * bd["e"][0] + dloc[:, 1:2] * bd["e"][1]
-                       + dloc[:, 2:3] * bd["e"][2]) / bd["w"][:, None]
-                v_nodes = v_all[off_node: off_node + nn]
-                res[base + off: base + off + 3 * nn] = \
-                    (-sub + v_nodes).reshape(-1) - bd["K"] @ U
-                res[base + off + 3 * nn: base + off + 3 * nn + 6] = \
-                    -bd["K"].T @ xb[: 3 * nn] + U
-                off += 3 * nn + 6
-                off_node += nn
-        return res
-
-    def _fiber_block_device(self, x_fib, v_fib_nodes, vel7=None):
-        """Per-fiber operator block: A x - vT_in + the two BC velocity
+    def _fiber_block(self, r, x_run, v_nodes, vel7=None):
+        """One run's fiber operator block: A x - vT_in + the two BC velocity
         corrections (fiber_fd.matvec, fiber_finite_difference.cpp:278-315),
         plus the y_BC link-condition rows when vel7 (nf, 7) is given
         (fiber matvec's v_boundary, f_c_fd.cpp:226).
-        x_fib (nf, 4n), v_fib_nodes (nf*n, 3) node-major -> (nf, 4n)."""
+        x_run (nf, 4n), v_nodes (nf*n, 3) node-major -> (nf, 4n)."""
         import torch
-        d = self._dev
-        nf, n = d["nf"], d["n"]
-        v_fib = v_fib_nodes.reshape(nf, n, 3).permute(0, 2, 1)       # (nf, 3, n)
-        vT = torch.zeros((nf, 4 * n), dtype=x_fib.dtype, device=x_fib.device)
+        nf, n = r["nf"], r["n"]
+        v_fib = v_nodes.reshape(nf, n, 3).permute(0, 2, 1)           # (nf, 3, n)
+        vT = torch.zeros((nf, 4 * n), dtype=x_run.dtype, device=x_run.device)
         vT[:, : 3 * n] = v_fib.reshape(nf, 3 * n)
-        tens = torch.einsum("ts,fis->fit", d["D1preT"],
-                            d["xs"] * v_fib).sum(dim=1)
+        tens = torch.einsum("ts,fis->fit", r["D1T"],
+                            r["xs_D1"] * v_fib).sum(dim=1)
         vT[:, 3 * n:] = tens
         vT_in = torch.zeros_like(vT)
-        vT_in[:, : 4 * n - 14] = vT @ d["P_ds"].T
-        res_fib = torch.bmm(d["A"], x_fib.unsqueeze(-1)).squeeze(-1) - vT_in
+        vT_in[:, : 4 * n - 14] = vT @ r["P_ds"].T
+        res_fib = torch.bmm(r["A"], x_run.unsqueeze(-1)).squeeze(-1) - vT_in
         bc_start = 4 * n - 14
-        res_fib[:, bc_start + 3] += (v_fib[:, :, 0] * d["xs"][:, :, 0]).sum(dim=1)
-        res_fib[:, bc_start + 10] += d["plus_vel"] * \
-            (v_fib[:, :, -1] * d["xs"][:, :, -1]).sum(dim=1)
+        res_fib[:, bc_start + 3] += (v_fib[:, :, 0] * r["xs"][:, :, 0]).sum(dim=1)
+        res_fib[:, bc_start + 10] += r["plus_vel"] * \
+            (v_fib[:, :, -1] * r["xs"][:, :, -1]).sum(dim=1)
         if vel7 is not None:
             res_fib[:, bc_start: bc_start + 7] += vel7
         return res_fib
 
-    def _apply_precond_device(self, x):
+    def apply_preconditioner(self, x):
+        """system.cpp:248-263, tensor in and out like apply_matvec: one
+        batched LU solve per run, own rows of M_inv against the global
+        shell vector, one dense LU solve per body."""
         import torch
-        d = self._dev
-        nf, n = d["nf"], d["n"]
-        sh_size = self.shell_sol_size
+        d = self._ops
         res = torch.empty_like(x)
-        res[: 4 * nf * n] = d["lu"].solve(x[: 4 * nf * n].reshape(nf, 4 * n)).reshape(-1)
+        for r in d["runs"]:
+            res[r["sol"]] = r["lu"].solve(
+                x[r["sol"]].reshape(r["nf"], 4 * r["n"])).reshape(-1)
+        off = d["fib_size"] + d["sh_size"]
         if self.shell:
-            x_sh = x[4 * nf * n: 4 * nf * n + sh_size]
-            res[4 * nf * n: 4 * nf * n + sh_size] = torch.mv(
+            res[d["fib_size"]: off] = torch.mv(
                 d["sh_Minv_T"].t(),
-                self.comm.gather_rows(x_sh.reshape(-1, 3)).reshape(-1))
-        if self.bodies:
-            off = 4 * nf * n + sh_size
-            for bd in d["bodies"]:
-                m = 3 * bd["n"] + 6
-                res[off: off + m] = bd["lu"].solve(
-                    x[off: off + m].unsqueeze(0)).squeeze(0)
-                off += m
+                self.comm.gather_rows(x[d["fib_size"]: off].reshape(-1, 3)).reshape(-1))
+        for bd in d.get("bodies", ()):
+            m = 3 * bd["n"] + 6
+            res[off: off + m] = bd["lu"].solve(x[off: off + m].unsqueeze(0)).squeeze(0)
+            off += m
         return res
 
-    def _device_mode(self, requested):
-        """solve(device_mode=): None picks the device-resident iteration
-        whenever it applies (uniform fibers on the HIP backend)."""
-        if requested is None:
-            return (bool(self.fibers) and self._uniform
-                    and isinstance(self.backend, HipBackend))
-        return requested
-
-    def solve(self, tol=1e-10, maxiter=200, restart=None, device_mode=None,
-              warm_start=None):
+    def solve(self, tol=1e-10, maxiter=200, restart=None, warm_start=None):
         """system.cpp:464-478 via the engine GMRES (right-preconditioned,
-        ICGS — solver_hydro.cpp:64-87). With uniform fibers on the HIP
-        backend the whole iteration runs device-resident, INCLUDING body
-        blocks (torch link conditions + body flow + body rows — default
-        since the round-2 GPU validation, tests/test_gpu_body.py::
-        test_device_resident_bodies_match_host_path). device_mode=False
-        forces the host matvec loop.
+        ICGS — solver_hydro.cpp:64-87). The whole iteration runs on the
+        backend's device, body blocks included.
 
         warm_start=True seeds GMRES with the PREVIOUS timestep's solution
         (the state changes O(dt) per step, so the initial residual starts
@@ -870,32 +740,17 @@ class SystemFD:
             import os
             warm_start = os.environ.get("SKELLY_WARM_START", "0") == "1"
         prev = getattr(self, "solution", None)
-        x0_np = prev if (warm_start and prev is not None
-                         and prev.shape == rhs.shape) else None
-
+        x0 = self._t(prev) if (warm_start and prev is not None
+                                       and prev.shape == rhs.shape) else None
+        b = self._t(rhs)
         # rank-local slices of a block-row-distributed vector: the GMRES
         # dots and norms reduce over ranks (the Tpetra/Belos dots)
-        distributed = self.comm.world > 1
-        if self._device_mode(device_mode):
-            self._build_device_operators()
-            b = self.backend._t(rhs)
-            x0 = self.backend._t(x0_np) if x0_np is not None else None
-            x, info = gmres(self._apply_matvec_device, b,
-                            precond=self._apply_precond_device,
-                            tol=tol, maxiter=maxiter, restart=restart, x0=x0,
-                            distributed=distributed)
-            if b.is_cuda:
-                self.backend.torch.cuda.synchronize()
-            self.solution = x.cpu().numpy()
-            return info
-
-        b = torch.from_numpy(rhs)
-        x0 = torch.from_numpy(x0_np) if x0_np is not None else None
-        mv = lambda v: torch.from_numpy(self.apply_matvec(v.numpy()))
-        pc = lambda v: torch.from_numpy(self.apply_preconditioner(v.numpy()))
-        x, info = gmres(mv, b, precond=pc, tol=tol, maxiter=maxiter,
-                        restart=restart, x0=x0, distributed=distributed)
-        self.solution = x.numpy()
+        x, info = gmres(self.apply_matvec, b, precond=self.apply_preconditioner,
+                        tol=tol, maxiter=maxiter, restart=restart, x0=x0,
+                        distributed=self.comm.world > 1)
+        if b.is_cuda:
+            torch.cuda.synchronize()
+        self.solution = x.cpu().numpy()
         return info
 
     def step(self, tol=1e-10, maxiter=200, restart=None):

@@ -1,7 +1,9 @@
 """Test-only backend over the CPU oracle for SystemFD orchestration tests.
 Lives under tests/ (not the product package) so nothing on the product path
 can import the oracle (oracle/ is test infrastructure; see oracle/__init__.py).
-Method contract matches skellysim_amd.system_fd.HipBackend."""
+Method contract matches skellysim_amd.system_fd.HipBackend's, on numpy
+arrays; having no device, it is a host backend, and SystemFD runs its one
+pipeline over it on CPU tensors."""
 
 import numpy as np
 
@@ -25,15 +27,6 @@ class OracleBackend:
     def self_stokeslet_batch(self, pts, eta):
         return np.stack([self.oracle.oseen_tensor(p, eta) for p in pts])
 
-    def batched_lu(self, A_batch):
-        import scipy.linalg as scla
-        lus = [scla.lu_factor(A) for A in A_batch]
-
-        def solve(rhs):
-            return np.stack([scla.lu_solve(lu, r) for lu, r in zip(lus, rhs)])
-
-        return solve
-
     def rotlet(self, centers, torques, r_trg, eta):
         return self.oracle.rotlet(centers, r_trg, torques, eta)
 
@@ -42,59 +35,3 @@ class OracleBackend:
 
     def stresslet_times_normal(self, nodes, normals, eta):
         return self.oracle.np_stresslet_times_normal(nodes, normals)
-
-    def shell_ops(self, A, M_inv):
-        return (lambda x: A @ x), (lambda x: M_inv @ x)
-
-
-class FakeDeviceBackend(OracleBackend):
-    """TEST-ONLY: drives the device-resident code paths on CPU torch tensors
-    (dev='cpu') so the device-mode orchestration — tensor layouts, gathers,
-    batched fiber blocks, row-block GEMVs — is testable without a GPU. The
-    pair-kernel device functions must be patched to oracle-backed fakes
-    (see patch_device_kernels_with_oracle)."""
-
-    def __init__(self):
-        super().__init__()
-        import torch
-        self.torch = torch
-        self.dev = torch.device("cpu")
-
-    def _t(self, a):
-        import torch
-        if torch.is_tensor(a):
-            return a.to(self.dev)
-        return torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
-
-
-def patch_device_kernels_with_oracle():
-    """Replace skellysim_amd.evaluator's device kernels with oracle-backed
-    CPU-tensor fakes (identical math by construction). TEST-ONLY; call in a
-    worker subprocess (or restore() in-process). Returns a restore
-    callable."""
-    import torch
-    import oracle
-    import skellysim_amd.evaluator as ev
-
-    saved = {k: getattr(ev, k) for k in
-             ("stokeslet_device", "stresslet_device",
-              "oseen_tensor_batched_device", "rotlet_device")}
-
-    def restore():
-        for k, v in saved.items():
-            setattr(ev, k, v)
-
-    def _np(t):
-        return np.ascontiguousarray(t.detach().cpu().numpy())
-
-    ev.stokeslet_device = lambda r, f, t, eta, out=None: torch.from_numpy(
-        oracle.stokeslet(_np(r), _np(f), _np(t), eta))
-    ev.stresslet_device = lambda r, f, t, eta, out=None: torch.from_numpy(
-        oracle.stresslet(_np(r), _np(f), _np(t), eta))
-    ev.oseen_tensor_batched_device = lambda pts, eta=1.0: torch.from_numpy(
-        np.stack([oracle.oseen_tensor(p, eta) for p in _np(pts)]))
-    ev.rotlet_device = lambda r, t, rho, eta=1.0, *a, **k: torch.from_numpy(
-        oracle.rotlet(_np(r), _np(t), _np(rho), eta))
-    return restore
-
-

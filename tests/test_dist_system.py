@@ -33,22 +33,16 @@ def _make_problem():
     return fx, fibers, bg
 
 
-def _dist_worker(rank, world, init_file, q, device_mode=False):
+def _dist_worker(rank, world, init_file, q):
     import torch.distributed as dist
     from skellysim_amd.system_dist import DistributedSystemFD, distribute_fibers
     from skellysim_amd.system_fd import Shell
-    from oracle_backend import (OracleBackend, FakeDeviceBackend,
-                                patch_device_kernels_with_oracle)
+    from oracle_backend import OracleBackend
     from skellysim_amd.sharded import shard_range
 
     dist.init_process_group("gloo", init_method=f"file://{init_file}",
                             rank=rank, world_size=world)
     try:
-        if device_mode:
-            patch_device_kernels_with_oracle()
-            backend = FakeDeviceBackend()
-        else:
-            backend = OracleBackend()
         fx, fibers, bg = _make_problem()
         N = len(fx["nodes"])
         a, b = shard_range(N, world, rank)
@@ -57,30 +51,26 @@ def _dist_worker(rank, world, init_file, q, device_mode=False):
         shell = Shell(fx["nodes"], fx["normals"], A_rows, M_rows)
         my_fibers = distribute_fibers(fibers, world, rank)
         sys_ = DistributedSystemFD(my_fibers, eta=1.0, dt=0.05, shell=shell,
-                                   shell_rows=(a, b), backend=backend,
+                                   shell_rows=(a, b), backend=OracleBackend(),
                                    background_flow=bg)
-        info = sys_.solve(tol=1e-11, maxiter=300, restart=100,
-                          device_mode=device_mode or None)
+        info = sys_.solve(tol=1e-11, maxiter=300, restart=100)
         q.put((rank, sys_.solution, sys_.fiber_sol_size, info["converged"]))
     finally:
         dist.destroy_process_group()
 
 
 @pytest.mark.timeout(300)
-@pytest.mark.parametrize("device_mode", [False, True],
-                         ids=["host", "device-layout"])
-def test_distributed_solve_matches_single_process(device_mode):
-    """device-layout runs the device-resident iteration under a world-2
-    communicator (SystemFD._apply_matvec_device) on CPU tensors with oracle-backed
-    kernel fakes — the orchestration (gathers, batched blocks, row-block
-    GEMVs, distributed GMRES on tensors) is what's under test; the HIP
-    kernels themselves are covered by the gpu-marked suites."""
+def test_distributed_solve_matches_single_process():
+    """The solve pipeline under a world-2 communicator, on CPU tensors over
+    the oracle backend — the orchestration (gathers, batched blocks,
+    row-block GEMVs, distributed GMRES on tensors) is what's under test; the
+    HIP kernels themselves are covered by the gpu-marked suites."""
     with tempfile.TemporaryDirectory() as td:
         init_file = os.path.join(td, "pg")
         ctx = mp.get_context("spawn")
         q = ctx.Queue()
         procs = [ctx.Process(target=_dist_worker,
-                             args=(r, WORLD, init_file, q, device_mode))
+                             args=(r, WORLD, init_file, q))
                  for r in range(WORLD)]
         for p in procs:
             p.start()
@@ -205,21 +195,21 @@ def test_distributed_body_solve_matches_single_process():
         assert np.allclose(quat, body.orientation, atol=1e-12)
 
 
-def test_distributed_bodies_stay_on_host_path():
-    """Bodies in the device-resident iteration are single-rank only: the
-    distributed system refuses a forced device mode when it has bodies and
-    never auto-selects it. (No process group: every collective is the
-    identity.)"""
+def test_distributed_bodies_without_group_equal_single_rank():
+    """A DistributedSystemFD with bodies and no process group is SystemFD's
+    code with identity collectives: the solutions are bitwise equal."""
     from skellysim_amd.system_dist import DistributedSystemFD
+    from skellysim_amd.system_fd import SystemFD
     from oracle_backend import OracleBackend
-    body, fibers = _body_problem()
-    sys_ = DistributedSystemFD(fibers, eta=1.0, dt=0.05,
-                               backend=OracleBackend(), bodies=[body])
-    with pytest.raises(NotImplementedError):
-        sys_.solve(device_mode=True)
-    info = sys_.solve()
-    assert info["converged"], info
-    assert not hasattr(sys_, "_dev")  # host path: no device operators built
+    sols = []
+    for cls in (DistributedSystemFD, SystemFD):
+        body, fibers = _body_problem()
+        sys_ = cls(fibers, eta=1.0, dt=0.05, backend=OracleBackend(),
+                   bodies=[body])
+        info = sys_.solve()
+        assert info["converged"], info
+        sols.append(sys_.solution)
+    assert np.array_equal(sols[0], sols[1])
 
 
 def _dist_triple_worker(rank, world, init_file, q):
@@ -369,9 +359,8 @@ def test_distributed_multistep_matches_single_process():
 
 
 def _make_mixed_problem():
-    """Mixed-discretization fibers (24/32 nodes) — exercises the
-    per-fiber LU fallback on the distributed host preconditioner path
-    (the uniform reshape used to crash on these)."""
+    """Mixed-discretization fibers (24/32 nodes) — one run per fiber on
+    each rank (the uniform reshape used to crash on these)."""
     from skellysim_amd.fiber_fd import FiberFD
     here = os.path.dirname(os.path.abspath(__file__))
     fx = np.load(os.path.join(here, "golden", "periphery_sphere_192.npz"))

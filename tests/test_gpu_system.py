@@ -40,41 +40,59 @@ def test_free_fiber_advection_hip(hip_backend):
     assert err < 1e-10, err
 
 
-def test_device_matvec_matches_host_matvec(hip_backend):
-    """The device-resident batched matvec/preconditioner must equal the
-    per-fiber host path on the same state."""
+def _shell_192():
     import os
-    from skellysim_amd.system_fd import SystemFD, Shell
-
+    from skellysim_amd.system_fd import Shell
     here = os.path.dirname(os.path.abspath(__file__))
     fx = np.load(os.path.join(here, "golden", "periphery_sphere_192.npz"))
-    shell = Shell(fx["nodes"], fx["normals"], fx["stresslet_plus_complementary"],
-                  fx["M_inv"])
+    return Shell(fx["nodes"], fx["normals"], fx["stresslet_plus_complementary"],
+                 fx["M_inv"])
+
+
+def test_device_matvec_matches_host_matvec(hip_backend):
+    """The batched matvec/preconditioner on device must equal the per-fiber
+    host oracle (tests/system_oracle.py, same HIP pair kernels) on the same
+    state; the fibers of the one batch alternate lengths 0.5 and 0.8."""
+    from skellysim_amd.system_fd import SystemFD
+    from system_oracle import pipeline_vs_host
+
     rng = np.random.default_rng(3)
-    fibs = [straight_fiber(n=32, length=0.5, direction=rng.uniform(-1, 1, 3),
-                           x0=rng.uniform(-0.25, 0.25, 3),
+    fibs = [straight_fiber(n=32, length=(0.5, 0.8)[k % 2],
+                           direction=rng.uniform(-1, 1, 3),
+                           x0=rng.uniform(-0.05, 0.05, 3),  # inside the unit shell
                            minus_clamped=(k % 2 == 0))
             for k in range(6)]
-    sys_ = SystemFD(fibs, eta=1.3, dt=0.05, shell=shell, backend=hip_backend,
+    sys_ = SystemFD(fibs, eta=1.3, dt=0.05, shell=_shell_192(),
+                    backend=hip_backend,
                     background_flow=lambda r: np.tile([0.05, 0, 0], (len(r), 1)))
-    sys_.prep_state_for_solver()
-    sys_._build_device_operators()
-    x = rng.uniform(-1, 1, sys_.fiber_sol_size + sys_.shell_sol_size)
-    x_t = hip_backend._t(x)
-    mv_dev = sys_._apply_matvec_device(x_t).cpu().numpy()
-    mv_host = sys_.apply_matvec(x)
-    rel = np.linalg.norm(mv_dev - mv_host) / np.linalg.norm(mv_host)
-    assert rel < 1e-12, rel
-    pc_dev = sys_._apply_precond_device(x_t).cpu().numpy()
-    pc_host = sys_.apply_preconditioner(x)
-    rel = np.linalg.norm(pc_dev - pc_host) / np.linalg.norm(pc_host)
-    assert rel < 1e-10, rel
+    rel_mv, rel_pc = pipeline_vs_host(sys_, seed=3)
+    assert rel_mv < 1e-12, rel_mv
+    assert rel_pc < 1e-10, rel_pc
+
+
+def test_mixed_runs_match_host_matvec(hip_backend):
+    """Three fibers with n = 16, 16, 32 (two runs) plus the 192-node shell
+    on device against the host oracle."""
+    from skellysim_amd.system_fd import SystemFD
+    from system_oracle import pipeline_vs_host
+
+    rng = np.random.default_rng(4)
+    fibs = [straight_fiber(n=n, length=length, direction=rng.uniform(-1, 1, 3),
+                           x0=rng.uniform(-0.25, 0.25, 3),
+                           minus_clamped=(k == 1))
+            for k, (n, length) in enumerate(((16, 0.5), (16, 0.4), (32, 0.5)))]
+    sys_ = SystemFD(fibs, eta=1.3, dt=0.05, shell=_shell_192(),
+                    backend=hip_backend)
+    assert sys_._fiber_runs() == [[0, 2], [2, 3]]
+    rel_mv, rel_pc = pipeline_vs_host(sys_, seed=4)
+    assert rel_mv < 1e-12, rel_mv
+    assert rel_pc < 1e-10, rel_pc
 
 
 def test_distributed_device_solve_world1(hip_backend):
-    """DistributedSystemFD's device-resident iteration on the real HIP path
-    (world 1: collectives are identities, everything else — gathered-source
-    matvec, row-block shell GEMVs, device GMRES — is the multi-GPU code)."""
+    """DistributedSystemFD's solve on the real HIP path (world 1:
+    collectives are identities, everything else — gathered-source matvec,
+    row-block shell GEMVs, device GMRES — is the multi-GPU code)."""
     import os
     from skellysim_amd.system_fd import SystemFD, Shell
     from skellysim_amd.system_dist import DistributedSystemFD
@@ -98,7 +116,7 @@ def test_distributed_device_solve_world1(hip_backend):
     sys_d = DistributedSystemFD(make_fibers(), eta=1.0, dt=0.05, shell=shell,
                                 shell_rows=(0, N), backend=hip_backend,
                                 background_flow=bg)
-    info = sys_d.solve(tol=1e-11, maxiter=300, device_mode=True)
+    info = sys_d.solve(tol=1e-11, maxiter=300)
     assert info["converged"], info
 
     sys_s = SystemFD(make_fibers(), eta=1.0, dt=0.05, shell=shell,

@@ -3,8 +3,8 @@
 spherical body (the reference's default body discretization,
 skelly_config.py:737-738) with N fibers attached at its nucleation sites,
 stepped through the coupled solve — the round-2 measurement target for the
-body path (it currently runs on the host matvec loop; the pair-kernel legs
-and the body's dense algebra are device work)."""
+body path (link conditions, body flow and body rows inside the
+device-resident iteration)."""
 
 import argparse
 import os

@@ -69,21 +69,21 @@ def build(nf, n, shell_fix):
 
 def profile(label, s, restart=150):
     rhs = s.prep_state_for_solver()
-    s._build_device_operators()
     b = s.backend._t(rhs)
     x = torch.randn_like(b)
 
-    mv = t_ms(lambda: s._apply_matvec_device(x))
-    pc = t_ms(lambda: s._apply_precond_device(x))
-    # preconditioner sub-parts
-    d = s._dev
-    nf, n = d["nf"], d["n"]
-    x_fib = x[: 4 * nf * n].reshape(nf, 4 * n).contiguous()
-    fib_ms = t_ms(lambda: d["lu"].solve(x_fib))
+    mv = t_ms(lambda: s.apply_matvec(x))
+    pc = t_ms(lambda: s.apply_preconditioner(x))
+    # preconditioner sub-parts (a uniform population: one run)
+    d = s._ops
+    r, = d["runs"]
+    x_fib = x[r["sol"]].reshape(r["nf"], 4 * r["n"]).contiguous()
+    fib_ms = t_ms(lambda: r["lu"].solve(x_fib))
     if s.shell:
-        sh = x[4 * nf * n: 4 * nf * n + s.shell_sol_size].contiguous()
-        shell_ms = t_ms(lambda: torch.mv(d["sh_Minv"], sh))
-        shell_t_ms = t_ms(lambda: torch.mv(d["sh_Minv"].t(), sh))
+        sh = x[d["fib_size"]: d["fib_size"] + d["sh_size"]].contiguous()
+        Minv = s.shell.M_inv  # row-major, as assembled on the device
+        shell_ms = t_ms(lambda: torch.mv(Minv, sh))
+        shell_t_ms = t_ms(lambda: torch.mv(Minv.t(), sh))
     else:
         shell_ms = shell_t_ms = 0.0
     print(f"  precond parts: fiber-solve {fib_ms:.2f} ms, "

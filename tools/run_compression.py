@@ -23,9 +23,6 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--t-final", type=float, default=5.0)
     ap.add_argument("--hip", action="store_true")
-    ap.add_argument("--device-mode", action="store_true",
-                    help="opt into the device-resident iteration (with "
-                         "bodies present the default is the host matvec)")
     args = ap.parse_args()
 
     t0 = time.perf_counter()
