@@ -207,6 +207,14 @@ int skelly_oseen_tensor_batched_device(const double *d_pts, double *d_G, long lo
  * register FMA chain — used to pin the roofline denominator. 0 on success. */
 int skelly_fp64_peak_tflops(double *out_tflops);
 
+/* What the pair loop's two non-FMA instruction kinds cost on the current
+ * device, measured as the fp64 FMA rate they take away when interleaved with
+ * independent v_fma_f64 (4 to 64): out3[0] one independent v_rsq_f64 and
+ * out3[1] one broadcast ds_read_b128, both in issue slots of a v_fma_f64
+ * (4 SIMD cycles each); out3[2] the TFLOP/s of the run without insertions.
+ * 0 on success. */
+int skelly_issue_cost_probe(double *out3);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,19 +12,30 @@
  * which used 32-thread blocks and accumulated into global memory every tile):
  *   - 256-thread blocks (4 wave64s), TPT targets per thread held in VGPRs;
  *     velocity accumulates in registers and is written once.
- *   - Sources staged through LDS in TILE=512-point tiles (36 KB stokeslet
- *     and oseen incl. the f/4 copy below, 48 KB stresslet). Inner-loop LDS
- *     reads are wave-uniform -> broadcast, conflict-free by construction.
+ *   - Sources reach the pair loop through scalar registers. Every lane of
+ *     a wave works on the same source, so a source is wave-uniform data: a
+ *     pack kernel (pack_sources, one launch ahead of pair_driver) writes the
+ *     launch's sources into the workspace as packed records {r[3], f[SRCDIM],
+ *     g[AUXDIM]}, and the pair loop reads them with scalar loads whose
+ *     addresses derive from kernel arguments, blockIdx and loop counters
+ *     only. Each source-consuming fp64 op has exactly one source operand,
+ *     which it takes straight from an SGPR pair: no LDS, no barrier and no
+ *     vector-side memory instruction in the loop. K::GROUP records are
+ *     loaded at a time, two groups in flight (the loads of the next group
+ *     issue before the arithmetic of the current one). The record buffer is
+ *     padded by one group so that a whole group may be read past the last
+ *     source; it is rebuilt on every call (strengths change every call) and
+ *     only ever read by the pair kernel.
  *   - fp64 rsqrt: raw v_rsq_f64 + one 3-op Newton step that returns
  *     R = 2/sqrt(x) (see rsq_x2). The factor 2 (and its powers R^3 = 8/r^3,
  *     R^5 = 32/r^5) never costs a pair-loop instruction: where it is global
  *     the host divides Params::scale by K::ACC_FOLD; stokeslet and oseen,
- *     which mix R and R^3, read a second LDS copy f/4 of the strength for
+ *     which mix R and R^3, read a second copy g = f/4 of the strength for
  *     the dot product so that every accumulator is exactly 2x the plain
  *     sum. All rescalings are powers of two -> results are bit-identical
  *     to the 4-op form (for values that stay normal fp64).
  *   - The r^2==0 mask (reference: kernels.cu:39,70) is off the fast path.
- *     Each tile is walked in CHUNK-source pieces: a wave saves its
+ *     Each slice is walked in CHUNK-source pieces: a wave saves its
  *     accumulators, runs the chunk unmasked (a coincident pair gives
  *     rsq(0) = inf, 0*inf = NaN, so the accumulator goes NaN), tests the
  *     accumulators, and only if some lane saw a NaN (wave-uniform branch)
@@ -36,7 +47,7 @@
  *     skelly_set_pair_fastpath(0) runs the masked path everywhere; by
  *     default small launches (under 128 chunks a block) stay masked too,
  *     see g_pair_fastpath.
- *   - Accumulation order per target is source order (tile-major), fixed ->
+ *   - Accumulation order per target is source order, fixed ->
  *     bit-reproducible for a given shard layout and slice count.
  *   - Source-split launches: gridDim.y source slices accumulate partials
  *     that a second kernel reduces in fixed slice order (deterministic).
@@ -47,7 +58,7 @@
  *     flagship's 977 blocks: 6 slices, 22.9 -> 23 workgroups a CU, instead of
  *     2 slices, 7.63 -> 8), with at least ~2048 sources a slice and the
  *     partial workspace capped. A pure function of shape, CU count and
- *     occupancy, so the summation order stays reproducible;
+ *     the functor's launch bound, so the summation order stays reproducible;
  *     skelly_set_pair_slices() forces a count for sweeps and tests.
  *   - The same driver evaluates the analytic velocity gradients of the four
  *     kernels (9 outputs a target, K::OUTDIM; functors further down).
@@ -69,17 +80,19 @@
 #include "pair_plan.hpp"
 
 #define BLOCK 256
-#define TILE 512
 
-/* Sources per unmasked chunk between two accumulator checks (multiple of
- * SKELLY_UNROLL, divides TILE). Measured on MI355X, profiles/pair_fastpath.md. */
+/* Sources per unmasked chunk between two accumulator checks, counted from the
+ * slice start. Measured on MI355X, profiles/pair_fastpath.md. */
 #ifndef SKELLY_CHUNK
 #define SKELLY_CHUNK 64
 #endif
 
-/* Sources per unrolled group of the velocity kernels' pair loop (even). */
-#ifndef SKELLY_UNROLL
-#define SKELLY_UNROLL 4
+/* Sources per group of scalar loads of the 9-double records (stokeslet,
+ * oseen, rotlet, normal-density stresslet: 18 SGPRs a source). Two groups are
+ * in flight, so a group costs 2 x 18 x GROUP of the ~100 SGPRs a wave has:
+ * 2 fits, 4 does not (profiles/pair_scalar.md). */
+#ifndef SKELLY_GROUP
+#define SKELLY_GROUP 2
 #endif
 
 /* R = 2/sqrt(x): v_rsq_f64 + one refinement step with the constant factor
@@ -122,17 +135,18 @@ __device__ inline double rsq_refined(double x) { return 0.5 * rsq_x2(x); }
  *              select out and must make a coincident pair detectable.
  *   NAN_PROBE  an unmasked coincident pair turns the accumulators NaN
  *              (else pair<false> lowers `zmin` to 0 on one).
- *   AUXDIM     doubles per source of the second LDS copy g = f/4 (0: none).
+ *   AUXDIM     doubles per source of the record's second copy g = f/4 (0: none).
  *   OUTDIM     accumulators and outputs per target (3 velocity components,
  *              9 for the gradient functors further down).
  *   MAX_TPT    most targets a thread holds (register budget).
- *   UNROLL     sources per unrolled group of the pair loop (even).
+ *   GROUP      sources per group of scalar record loads (SGPR budget: two
+ *              groups of GROUP x 2 x (3 + SRCDIM + AUXDIM) SGPRs are live).
  *   FASTPATH   the unmasked chunk-rerun path is wired (needs HAS_MASK). */
 
 struct VelocityTraits {
     static constexpr int OUTDIM = 3;
     static constexpr int MAX_TPT = 4;
-    static constexpr int UNROLL = SKELLY_UNROLL;
+    static constexpr int GROUP = SKELLY_GROUP;
     static constexpr bool FASTPATH = true;
 };
 
@@ -177,6 +191,7 @@ struct Stokeslet : VelocityTraits {
 
 struct Stresslet : VelocityTraits {
     static constexpr int MIN_WAVES = 2;
+    static constexpr int GROUP = 1; /* 24 SGPRs a source */
     static constexpr int SRCDIM = 9;
     static constexpr int AUXDIM = 0;
     static constexpr bool HAS_MASK = true;
@@ -376,8 +391,8 @@ struct StressletNormalDensity : VelocityTraits {
  * Each formula is the exact derivative of the matching velocity kernel inside
  * each of its branches (the regularized branches differentiate the
  * regularized expression). Nine accumulators a target leave room for fewer
- * targets per thread and a shorter unroll than the velocity kernels
- * (MAX_TPT, UNROLL; numbers in DESIGN.md), and every pair goes through the
+ * targets per thread than the velocity kernels (MAX_TPT; numbers in
+ * DESIGN.md), and every pair goes through the
  * r == 0 mask (FASTPATH off), so the result cannot depend on
  * skelly_set_pair_fastpath. */
 
@@ -390,7 +405,7 @@ struct StressletNormalDensity : VelocityTraits {
 
 struct GradTraits {
     static constexpr int OUTDIM = 9;
-    static constexpr int UNROLL = 2;
+    static constexpr int GROUP = SKELLY_GROUP;
     static constexpr int AUXDIM = 0;
     static constexpr bool FASTPATH = false;
     static constexpr bool NAN_PROBE = false;
@@ -460,6 +475,7 @@ struct StokesletGrad : GradTraits {
  * the -3 rides in Params::scale. b.d = 2C. */
 struct StressletGrad : GradTraits {
     static constexpr int MIN_WAVES = 3;
+    static constexpr int GROUP = 1; /* 24 SGPRs a source */
     static constexpr int MAX_TPT = SKELLY_DLGRAD_TPT;
     static constexpr int SRCDIM = 9;
     static constexpr bool HAS_MASK = true;
@@ -562,62 +578,118 @@ struct RotletGrad : GradTraits {
 
 /* ---- driver ----------------------------------------------------------- */
 
-/* N doubles (N even; 0 allowed) from a 16-byte aligned LDS address. */
+/* Doubles of one packed source record {r[3], f[SRCDIM], g[AUXDIM]}. */
+template <typename K>
+constexpr int rec_doubles() {
+    return 3 + K::SRCDIM + K::AUXDIM;
+}
+
+/* Records the buffer holds for n_src sources: one group of padding, so that
+ * the pair loop may load a whole group past the last source. */
+template <typename K>
+constexpr long long rec_count(long long n_src) {
+    return n_src + K::GROUP;
+}
+
+/* Write the launch's sources as packed records, the padding as zeros. One
+ * thread per double of the buffer (coalesced stores); g = 0.25 * f is an
+ * exact power-of-two product. */
+template <typename K>
+__global__ __launch_bounds__(BLOCK) void pack_sources(const double *__restrict__ r_src,
+                                                      const double *__restrict__ f_src,
+                                                      double *__restrict__ rec,
+                                                      long long n_src) {
+    constexpr int R = rec_doubles<K>();
+    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= R * rec_count<K>(n_src))
+        return;
+    const long long s = i / R;
+    const int j = (int)(i - s * R);
+    double v = 0.0;
+    if (s < n_src) {
+        if (j < 3)
+            v = r_src[3 * s + j];
+        else if (j < 3 + K::SRCDIM)
+            v = f_src[K::SRCDIM * s + (j - 3)];
+        else /* AUXDIM == SRCDIM where present */
+            v = 0.25 * f_src[K::SRCDIM * s + (j - 3 - K::SRCDIM)];
+    }
+    rec[i] = v;
+}
+
+/* One group of records into registers. `src` is block-uniform (kernel
+ * arguments, blockIdx and loop counters only) and the buffer is never written
+ * by this kernel, so these are scalar loads into SGPRs. */
 template <int N>
-__device__ __forceinline__ void lds_read16(double *dst, const double *src) {
-    typedef double d2 __attribute__((ext_vector_type(2), may_alias));
-    static_assert(N % 2 == 0, "whole 16-byte vectors only");
+__device__ __forceinline__ void load_group(double (&dst)[N], const double *__restrict__ src) {
+    /* Scalar loads return out of order, so the only wait there is is for all
+     * of them: take the wait for the group loaded before (the one about to
+     * be used) here, ahead of these loads. Behind them it would wait for
+     * these as well. s_waitcnt lgkmcnt(0) with vmcnt and expcnt left alone. */
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int i = 0; i < N / 2; ++i) {
-        const d2 v = reinterpret_cast<const d2 *>(src)[i];
-        dst[2 * i] = v.x;
-        dst[2 * i + 1] = v.y;
+    for (int i = 0; i < N; ++i)
+        dst[i] = src[i];
+    /* Pin the loads here: left alone, the scheduler sinks them below the
+     * arithmetic of the group before, right in front of their own wait. */
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+/* The first `count` sources of a loaded group (all of them with FULL) onto
+ * this thread's TPT targets, in source order. */
+template <typename K, int TPT, bool MASKED, bool FULL>
+__device__ __forceinline__ void pair_group(const double (&g)[K::GROUP * rec_doubles<K>()],
+                                           const int count, const double (&tp)[TPT][3],
+                                           double (&acc)[TPT][K::OUTDIM],
+                                           const typename K::Params &params, unsigned &zmin) {
+    constexpr int R = rec_doubles<K>();
+#pragma unroll
+    for (int u = 0; u < K::GROUP; ++u) {
+        if (!FULL && u >= count)
+            break;
+#pragma unroll
+        for (int k = 0; k < TPT; ++k)
+            K::template pair<MASKED>(tp[k], g + R * u, g + R * u + 3, g + R * u + 3 + K::SRCDIM,
+                                     acc[k], params, zmin);
     }
 }
 
-/* Sources [s, s_end) of the staged tile onto this thread's TPT targets, in
- * source order. Unrolled by U sources: all U sources' LDS reads issue
- * together (one lgkmcnt wait per U sources instead of several per source)
- * and their v_rsq/refine chains interleave. */
+/* The n >= 1 sources whose records start at `rec` onto this thread's TPT
+ * targets, in source order. Two groups of K::GROUP records are in flight:
+ * the scalar loads of the next group issue before the arithmetic of the
+ * current one (scalar loads return out of order, so the only usable wait is
+ * for all of them, and it falls behind a whole group of arithmetic). Loads
+ * reach at most K::GROUP - 1 records past source n: the buffer's padding.
+ * `a` comes in with the loads of the group at `rec` issued (load_group) and,
+ * when n is a multiple of 2 * K::GROUP, goes out with those of the group at
+ * source n issued: a chunk hands the next one its first group, so that only
+ * a slice's first group is waited for with nothing to compute meanwhile. */
 template <typename K, int TPT, bool MASKED>
-__device__ __forceinline__ void pair_span(const double *lds_r, const double *lds_f,
-                                          const double *lds_g, int s, const int s_end,
+__device__ __forceinline__ void pair_span(const double *__restrict__ rec, const int n,
+                                          double (&a)[K::GROUP * rec_doubles<K>()],
                                           const double (&tp)[TPT][3],
                                           double (&acc)[TPT][K::OUTDIM],
                                           const typename K::Params &params, unsigned &zmin) {
-    constexpr int U = K::UNROLL;
-    constexpr int A = K::AUXDIM > 0 ? K::AUXDIM : 1;
-    /* Callers start at a multiple of U (U even), so each group of U sources
-     * begins 16-byte aligned in all three arrays: read it as 16-byte
-     * vectors, or the reads come out as ds_read2_b64 with one address
-     * register per array. */
-    static_assert(U % 2 == 0, "the 16-byte LDS reads below need an even unroll");
-    for (; s + U <= s_end; s += U) {
-        double sp[U * 3], sf[U * K::SRCDIM], sg[U * A];
-        lds_read16<U * 3>(sp, lds_r + 3 * s);
-        lds_read16<U * K::SRCDIM>(sf, lds_f + K::SRCDIM * s);
-        lds_read16<U * K::AUXDIM>(sg, lds_g + K::AUXDIM * s);
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int k = 0; k < TPT; ++k)
-                K::template pair<MASKED>(tp[k], sp + 3 * u, sf + K::SRCDIM * u,
-                                         sg + K::AUXDIM * u, acc[k], params, zmin);
+    constexpr int G = K::GROUP;
+    constexpr int R = rec_doubles<K>();
+    double b[G * R];
+    int s = 0;
+    for (; s + 2 * G <= n; s += 2 * G) {
+        load_group(b, rec + R * (s + G));
+        pair_group<K, TPT, MASKED, true>(a, G, tp, acc, params, zmin);
+        load_group(a, rec + R * (s + 2 * G));
+        pair_group<K, TPT, MASKED, true>(b, G, tp, acc, params, zmin);
     }
-    for (; s < s_end; ++s) {
-        double sp[3], sf[K::SRCDIM], sg[A];
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            sp[j] = lds_r[3 * s + j];
-#pragma unroll
-        for (int j = 0; j < K::SRCDIM; ++j)
-            sf[j] = lds_f[K::SRCDIM * s + j];
-#pragma unroll
-        for (int j = 0; j < K::AUXDIM; ++j)
-            sg[j] = lds_g[K::AUXDIM * s + j];
-#pragma unroll
-        for (int k = 0; k < TPT; ++k)
-            K::template pair<MASKED>(tp[k], sp, sf, sg, acc[k], params, zmin);
+    /* 0 .. 2G-1 sources left; `a` holds the group at s */
+    const int left = n - s;
+    if (left > G) {
+        load_group(b, rec + R * (s + G));
+        pair_group<K, TPT, MASKED, true>(a, G, tp, acc, params, zmin);
+        pair_group<K, TPT, MASKED, false>(b, left - G, tp, acc, params, zmin);
+    } else {
+        pair_group<K, TPT, MASKED, false>(a, left, tp, acc, params, zmin);
     }
 }
 
@@ -629,16 +701,12 @@ __device__ __forceinline__ void pair_span(const double *lds_r, const double *lds
  * fixed slice order (deterministic) and applies the finish scale.
  * fastpath != 0 runs each chunk unmasked first (see the file header). */
 template <typename K, int TPT, bool PARTIAL = false>
-__global__ __launch_bounds__(BLOCK, K::MIN_WAVES) void pair_driver(const double *__restrict__ r_src,
-                                                     const double *__restrict__ f_src,
+__global__ __launch_bounds__(BLOCK, K::MIN_WAVES) void pair_driver(const double *__restrict__ rec,
                                                      const double *__restrict__ r_trg,
                                                      double *__restrict__ u_trg,
                                                      long long n_src, long long n_trg,
+                                                     long long slice_len,
                                                      typename K::Params params, int fastpath) {
-    __shared__ __attribute__((aligned(16))) double lds[TILE * (3 + K::SRCDIM + K::AUXDIM)];
-    double *lds_r = lds;
-    double *lds_f = lds + TILE * 3;
-    double *lds_g = lds + TILE * (3 + K::SRCDIM);
     const int tid = threadIdx.x;
     const long long base = (long long)blockIdx.x * (BLOCK * TPT);
 
@@ -657,68 +725,70 @@ __global__ __launch_bounds__(BLOCK, K::MIN_WAVES) void pair_driver(const double 
             acc[k][j] = 0.0;
     }
 
+    /* An empty use of the target coordinates: the wait for their loads falls
+     * here, once, instead of in the pair loop as one counted wait a target. */
+#pragma unroll
+    for (int k = 0; k < TPT; ++k)
+        asm volatile("" : "+v"(tp[k][0]), "+v"(tp[k][1]), "+v"(tp[k][2]));
+
+    /* slice_len = ceil(n_src / gridDim.y) comes from the host: a 64-bit
+     * division here would leave the slice start, and every record address
+     * derived from it, in vector registers. */
     long long src_begin = 0, src_end = n_src;
     if (PARTIAL) {
-        const long long chunk = (n_src + gridDim.y - 1) / gridDim.y;
-        src_begin = (long long)blockIdx.y * chunk;
-        src_end = src_begin + chunk < n_src ? src_begin + chunk : n_src;
+        src_begin = (long long)blockIdx.y * slice_len;
+        src_end = src_begin + slice_len < n_src ? src_begin + slice_len : n_src;
     }
 
-    for (long long tile0 = src_begin; tile0 < src_end; tile0 += TILE) {
-        const int m = (int)((src_end - tile0 < TILE) ? (src_end - tile0) : TILE);
-        __syncthreads();
-        for (int i = tid; i < m * 3; i += BLOCK)
-            lds_r[i] = r_src[tile0 * 3 + i];
-        for (int i = tid; i < m * K::SRCDIM; i += BLOCK) {
-            const double v = f_src[tile0 * K::SRCDIM + i];
-            lds_f[i] = v;
-            if (K::AUXDIM > 0) /* AUXDIM == SRCDIM where present */
-                lds_g[i] = 0.25 * v;
-        }
-        __syncthreads();
-
+    /* Kernels with a wired fast path walk the slice in chunks of
+     * SKELLY_CHUNK sources counted from the slice start. The others have no
+     * mask to skip, or always go through it: one span over the slice (in
+     * pieces that keep pair_span's counters 32-bit). */
+    constexpr bool CHUNKED = K::HAS_MASK && K::FASTPATH;
+    constexpr int SPAN = CHUNKED ? SKELLY_CHUNK : (1 << 30);
+    constexpr int R = rec_doubles<K>();
+    static_assert(SPAN % (2 * K::GROUP) == 0, "a full span must hand on the next group");
+    /* the group at the start of the span, loaded by the span before */
+    double first[K::GROUP * R];
+    if (src_begin < src_end)
+        load_group(first, rec + R * src_begin);
+    for (long long c0 = src_begin; c0 < src_end; c0 += SPAN) {
+        const int n = (int)((src_end - c0 < SPAN) ? (src_end - c0) : SPAN);
+        const double *span = rec + R * c0;
         unsigned zmin = ~0u;
-        if (!K::HAS_MASK || !K::FASTPATH) {
-            /* no mask to skip, or always through it: one span over the tile */
-            pair_span<K, TPT, K::HAS_MASK>(lds_r, lds_f, lds_g, 0, m, tp, acc, params, zmin);
+        if (!CHUNKED) {
+            pair_span<K, TPT, K::HAS_MASK>(span, n, first, tp, acc, params, zmin);
             continue;
         }
-        static_assert(SKELLY_CHUNK % K::UNROLL == 0 && TILE % SKELLY_CHUNK == 0,
-                      "chunks must hold whole unroll groups and tile the LDS tile");
-        for (int ci = 0; ci * SKELLY_CHUNK < m; ++ci) {
-            /* a visible multiple of CHUNK keeps the b128 LDS reads provably aligned */
-            const int c0 = ci * SKELLY_CHUNK;
-            const int c1 = c0 + SKELLY_CHUNK < m ? c0 + SKELLY_CHUNK : m;
-            bool masked = !fastpath;
-            if (fastpath) {
-                double saved[TPT][OD];
+        bool masked = !fastpath;
+        if (fastpath) {
+            double saved[TPT][OD];
+#pragma unroll
+            for (int k = 0; k < TPT; ++k)
+#pragma unroll
+                for (int j = 0; j < OD; ++j)
+                    saved[k][j] = acc[k][j];
+            pair_span<K, TPT, false>(span, n, first, tp, acc, params, zmin);
+            bool hit = zmin == 0u;
+            if (K::NAN_PROBE) {
 #pragma unroll
                 for (int k = 0; k < TPT; ++k)
 #pragma unroll
                     for (int j = 0; j < OD; ++j)
-                        saved[k][j] = acc[k][j];
-                zmin = ~0u;
-                pair_span<K, TPT, false>(lds_r, lds_f, lds_g, c0, c1, tp, acc, params, zmin);
-                bool hit = zmin == 0u;
-                if (K::NAN_PROBE) {
-#pragma unroll
-                    for (int k = 0; k < TPT; ++k)
-#pragma unroll
-                        for (int j = 0; j < OD; ++j)
-                            hit |= acc[k][j] != acc[k][j];
-                }
-                masked = __any(hit); /* wave-uniform */
-                if (masked) {
-#pragma unroll
-                    for (int k = 0; k < TPT; ++k)
-#pragma unroll
-                        for (int j = 0; j < OD; ++j)
-                            acc[k][j] = saved[k][j];
-                }
+                        hit |= acc[k][j] != acc[k][j];
             }
-            if (masked)
-                pair_span<K, TPT, true>(lds_r, lds_f, lds_g, c0, c1, tp, acc, params, zmin);
+            masked = __any(hit); /* wave-uniform */
+            if (masked) {
+#pragma unroll
+                for (int k = 0; k < TPT; ++k)
+#pragma unroll
+                    for (int j = 0; j < OD; ++j)
+                        acc[k][j] = saved[k][j];
+                load_group(first, span); /* the rerun starts over */
+            }
         }
+        if (masked)
+            pair_span<K, TPT, true>(span, n, first, tp, acc, params, zmin);
     }
 
     /* Recompute the target index from an opaque copy of tid: otherwise the
@@ -788,7 +858,8 @@ struct Knob {
 };
 } // namespace
 
-/* Optional persistent split-K workspace (SKELLY_PERSISTENT_WS=1): replaces
+/* Optional persistent launch workspace (SKELLY_PERSISTENT_WS=1; the source
+ * records of every launch and the partials of the split ones): replaces
  * the per-launch hipMallocAsync/hipFreeAsync pair with a grow-only buffer
  * cached per stream. Reuse across launches is safe because launches on one
  * stream are ordered; outgrown blocks are RETIRED (never freed or reused —
@@ -845,42 +916,27 @@ static Knob g_pair_fastpath{"SKELLY_PAIR_FASTPATH", 1,
  * pair_plan.hpp decides. n >= 1, from skelly_set_pair_slices() or else
  * SKELLY_PAIR_SLICES: exactly n slices (clamped to n_src and to the
  * gridDim.y limit), for sweeps and tests; slices may then be shorter than a
- * tile, start anywhere, and the last ones may be empty (they write zeros). */
+ * chunk, start anywhere, and the last ones may be empty (they write zeros). */
 static Knob g_pair_slices{"SKELLY_PAIR_SLICES", 0, [](int v) { return v < 0 ? 0 : v; }};
 
-/* What the planner needs to know of the device, asked once per device and
- * kernel: CU count and how many workgroups of the split instantiation a CU
- * holds at once (stresslet 2, the others 3). A launch only reads the cached
- * pair. */
-struct PairDeviceInfo {
-    int n_cu;
-    int wg_per_cu;
-};
-
-template <typename K, int TPT>
-static PairDeviceInfo pair_device_info() {
+/* The device's CU count for the planner, asked once per device (256 on
+ * MI355X, the default if the query fails). */
+static int pair_device_cus() {
     static std::mutex mu;
-    static std::map<int, PairDeviceInfo> cache;
+    static std::map<int, int> cache;
     int dev = 0;
     (void)hipGetDevice(&dev);
     std::lock_guard<std::mutex> lk(mu);
     auto it = cache.find(dev);
     if (it != cache.end())
         return it->second;
-    /* defaults: MI355X; 256-thread blocks on 4 SIMDs, so waves/SIMD ==
-     * workgroups/CU */
-    PairDeviceInfo info{256, K::MIN_WAVES};
+    int n_cu = 256;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-        info.n_cu = prop.multiProcessorCount;
-    int wg = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg, pair_driver<K, TPT, true>, BLOCK, 0) ==
-            hipSuccess &&
-        wg > 0)
-        info.wg_per_cu = wg;
+        n_cu = prop.multiProcessorCount;
     (void)hipGetLastError();
-    cache[dev] = info;
-    return info;
+    cache[dev] = n_cu;
+    return n_cu;
 }
 
 /* f(std::integral_constant<int, TPT>) for the runtime tpt, instantiating only
@@ -898,8 +954,8 @@ static auto dispatch_tpt(int tpt, F &&f) {
 
 template <typename K>
 static inline int pick_tpt(long long n_trg) {
-    /* Prefer 4 targets/thread (amortizes the per-source LDS broadcast reads
-     * 4x), up to what the functor's registers hold; occupancy for small
+    /* Prefer 4 targets/thread (amortizes the per-source scalar loads 4x),
+     * up to what the functor's registers hold; occupancy for small
      * target counts is recovered by source splitting, not by shrinking TPT. */
     if (K::MAX_TPT >= 4 && n_trg >= BLOCK * 4)
         return 4;
@@ -922,32 +978,22 @@ static hipError_t launch_pair(const double *r_src, const double *f_src, const do
     /* Source slices from the CU load-balance model (pair_plan.hpp): the
      * slice count that leaves the CUs the least uneven numbers of
      * workgroups, within the slice-length floor and the workspace cap. */
-    const PairDeviceInfo info = dispatch_tpt<K>(
-        tpt, [](auto t) { return pair_device_info<K, decltype(t)::value>(); });
+    /* wg_per_cu: the functor's launch bound, as the planner's constants were
+     * fitted with. Without LDS the occupancy query answers more, and the
+     * plans (with them the summation order) are not to move with it. */
     const PairPlan plan =
         pair_plan(n_src, n_trg, K::MAX_TPT, K::OUTDIM, g_pair_fastpath.get(),
-                  PAIR_FASTPATH_MIN_SRC, info.n_cu, info.wg_per_cu, g_pair_slices.get());
+                  PAIR_FASTPATH_MIN_SRC, pair_device_cus(), K::MIN_WAVES, g_pair_slices.get());
     const int n_slices = plan.n_slices;
     const int fast = plan.fast;
 
-    dim3 block(BLOCK);
-    /* pair_driver<K, tpt, PARTIAL> over `grid` into `dst` */
-    auto launch_driver = [&](auto partial, dim3 grid, double *dst) {
-        dispatch_tpt<K>(tpt, [&](auto t) {
-            hipLaunchKernelGGL((pair_driver<K, decltype(t)::value, decltype(partial)::value>),
-                               grid, block, 0, stream, r_src, f_src, r_trg, dst, n_src, n_trg,
-                               params, fast);
-        });
-    };
-    if (n_slices == 1) {
-        launch_driver(std::false_type{}, dim3((unsigned)blocks), u_trg);
-        return hipGetLastError();
-    }
-
-    /* split path: same TPT, gridDim.y source slices into a partial buffer */
+    /* Workspace: the packed source records, then (split launches) the
+     * partials of every slice. */
+    const size_t rec_doubles_total = (size_t)rec_doubles<K>() * rec_count<K>(n_src);
+    const size_t partial_doubles = n_slices > 1 ? (size_t)n_slices * K::OUTDIM * n_trg : 0;
+    const size_t ws_bytes = (rec_doubles_total + partial_doubles) * sizeof(double);
     double *workspace = nullptr;
     bool pooled = false;
-    const size_t ws_bytes = (size_t)n_slices * K::OUTDIM * n_trg * sizeof(double);
     if (g_persistent_ws.get() != 0) {
         workspace = persistent_ws(stream, ws_bytes);
         pooled = workspace != nullptr;
@@ -957,10 +1003,31 @@ static hipError_t launch_pair(const double *r_src, const double *f_src, const do
         if (err != hipSuccess)
             return err;
     }
-    launch_driver(std::true_type{}, dim3((unsigned)blocks, (unsigned)n_slices), workspace);
-    const long long rblocks = (K::OUTDIM * n_trg + BLOCK - 1) / BLOCK;
-    hipLaunchKernelGGL((reduce_partials<K>), dim3((unsigned)rblocks), block, 0, stream,
-                       workspace, u_trg, n_trg, n_slices, params);
+    double *rec = workspace;
+    double *partials = workspace + rec_doubles_total;
+
+    const long long slice_len = (n_src + n_slices - 1) / n_slices;
+    dim3 block(BLOCK);
+    const long long pblocks = ((long long)rec_doubles_total + BLOCK - 1) / BLOCK;
+    hipLaunchKernelGGL((pack_sources<K>), dim3((unsigned)pblocks), block, 0, stream, r_src, f_src,
+                       rec, n_src);
+    /* pair_driver<K, tpt, PARTIAL> over `grid` into `dst` */
+    auto launch_driver = [&](auto partial, dim3 grid, double *dst) {
+        dispatch_tpt<K>(tpt, [&](auto t) {
+            hipLaunchKernelGGL((pair_driver<K, decltype(t)::value, decltype(partial)::value>),
+                               grid, block, 0, stream, rec, r_trg, dst, n_src, n_trg, slice_len,
+                               params, fast);
+        });
+    };
+    if (n_slices == 1) {
+        launch_driver(std::false_type{}, dim3((unsigned)blocks), u_trg);
+    } else {
+        /* split path: same TPT, gridDim.y source slices into the partials */
+        launch_driver(std::true_type{}, dim3((unsigned)blocks, (unsigned)n_slices), partials);
+        const long long rblocks = (K::OUTDIM * n_trg + BLOCK - 1) / BLOCK;
+        hipLaunchKernelGGL((reduce_partials<K>), dim3((unsigned)rblocks), block, 0, stream,
+                           partials, u_trg, n_trg, n_slices, params);
+    }
     hipError_t err = hipGetLastError();
     if (pooled)
         return err;
@@ -1164,6 +1231,123 @@ hipError_t run_fp64_peak(double *out_tflops) {
         return err;
     const double flops = 2.0 * 16.0 * (double)iters * (double)blocks * threads;
     *out_tflops = flops / (ms * 1e-3) / 1e12;
+    return hipSuccess;
+}
+
+/* ---- issue-cost probe (what the pair loop's non-FMA instructions cost) ---
+ * The body of fp64_fma_peak_kernel four times over (64 independent
+ * v_fma_f64 on 16 accumulators) with 4 instructions of one kind put in front,
+ * about the pair loop's mix (16 v_rsq_f64 and 18 ds_read_b128 to 320 fp64
+ * ops):
+ *   PROBE_NONE  nothing (the base time);
+ *   PROBE_RSQ   4 independent v_rsq_f64;
+ *   PROBE_LDS   4 ds_read_b128 of one address for all lanes (a broadcast),
+ *               waited for behind the 64 FMAs.
+ * What an inserted instruction costs is the FMA rate it takes away. */
+enum { PROBE_NONE = 0, PROBE_RSQ = 1, PROBE_LDS = 2 };
+constexpr int PROBE_FMA = 64, PROBE_INSERTED = 4, PROBE_ITERS = 25000;
+
+template <int MODE>
+__global__ __launch_bounds__(256) void issue_probe_kernel(double *out, int iters) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    __shared__ __attribute__((aligned(16))) double lds[2 * PROBE_INSERTED];
+    if (threadIdx.x < 2 * PROBE_INSERTED)
+        lds[threadIdx.x] = 1.0 + threadIdx.x;
+    __syncthreads();
+    /* the low 32 bits of a flat LDS address are the LDS offset */
+    const unsigned lds_addr = (unsigned)(size_t)lds;
+    double a[16], x[PROBE_INSERTED];
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        a[k] = 1.0 + 1e-9 * threadIdx.x + 0.1 * k;
+#pragma unroll
+    for (int j = 0; j < PROBE_INSERTED; ++j)
+        x[j] = 2.0 + j + 1e-3 * threadIdx.x;
+    const double b = 1.0 + 1e-12, c = 1e-12;
+    for (int i = 0; i < iters; ++i) {
+        double y[PROBE_INSERTED];
+        d2 v[PROBE_INSERTED];
+        if (MODE == PROBE_RSQ) {
+#pragma unroll
+            for (int j = 0; j < PROBE_INSERTED; ++j)
+                asm volatile("v_rsq_f64 %0, %1" : "=v"(y[j]) : "v"(x[j]));
+        }
+        if (MODE == PROBE_LDS) {
+#pragma unroll
+            for (int j = 0; j < PROBE_INSERTED; ++j)
+                asm volatile("ds_read_b128 %0, %1 offset:%2"
+                             : "=v"(v[j])
+                             : "v"(lds_addr), "i"(16 * j));
+        }
+#pragma unroll
+        for (int r = 0; r < PROBE_FMA / 16; ++r)
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                a[k] = __builtin_fma(a[k], b, c);
+        /* the destinations stay allocated until the reads have landed */
+        if (MODE == PROBE_LDS) {
+            asm volatile("s_waitcnt lgkmcnt(0)");
+#pragma unroll
+            for (int j = 0; j < PROBE_INSERTED; ++j)
+                asm volatile("" ::"v"(v[j]));
+        }
+        if (MODE == PROBE_RSQ) {
+#pragma unroll
+            for (int j = 0; j < PROBE_INSERTED; ++j)
+                asm volatile("" ::"v"(y[j]));
+        }
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        s += a[k];
+    if (s == -1.0) /* never true; defeats DCE without a store per thread */
+        out[blockIdx.x] = s;
+}
+
+template <int MODE>
+static hipError_t time_issue_probe(double *d, hipEvent_t t0, hipEvent_t t1, float *ms) {
+    const int iters = PROBE_ITERS, blocks = 2048, threads = 256;
+    hipLaunchKernelGGL(issue_probe_kernel<MODE>, dim3(blocks), dim3(threads), 0, 0, d, iters / 10);
+    (void)hipEventRecord(t0);
+    hipLaunchKernelGGL(issue_probe_kernel<MODE>, dim3(blocks), dim3(threads), 0, 0, d, iters);
+    (void)hipEventRecord(t1);
+    const hipError_t err = hipEventSynchronize(t1);
+    (void)hipEventElapsedTime(ms, t0, t1);
+    return err;
+}
+
+/* out[0], out[1]: what one v_rsq_f64 and one broadcast ds_read_b128 cost, in
+ * issue slots of a v_fma_f64 (4 cycles of the SIMD each):
+ * (t_with - t_base) / t_base * PROBE_FMA / PROBE_INSERTED. out[2]: the base
+ * run's TFLOP/s, to check it against run_fp64_peak. The three runs are taken
+ * twice, alternating; the second round is reported. */
+hipError_t run_issue_cost_probe(double *out) {
+    const int blocks = 2048;
+    double *d;
+    hipError_t err = hipMalloc(&d, blocks * sizeof(double));
+    if (err != hipSuccess)
+        return err;
+    hipEvent_t t0, t1;
+    (void)hipEventCreate(&t0);
+    (void)hipEventCreate(&t1);
+    float base = 0, rsq = 0, lds = 0;
+    for (int round = 0; round < 2 && err == hipSuccess; ++round) {
+        err = time_issue_probe<PROBE_NONE>(d, t0, t1, &base);
+        if (err == hipSuccess)
+            err = time_issue_probe<PROBE_RSQ>(d, t0, t1, &rsq);
+        if (err == hipSuccess)
+            err = time_issue_probe<PROBE_LDS>(d, t0, t1, &lds);
+    }
+    (void)hipEventDestroy(t0);
+    (void)hipEventDestroy(t1);
+    (void)hipFree(d);
+    if (err != hipSuccess)
+        return err;
+    const double per = (double)PROBE_FMA / PROBE_INSERTED;
+    out[0] = (rsq - base) / base * per;
+    out[1] = (lds - base) / base * per;
+    out[2] = 2.0 * PROBE_FMA * (double)PROBE_ITERS * blocks * 256 / (base * 1e-3) / 1e12;
     return hipSuccess;
 }
 

@@ -42,6 +42,9 @@ hipError_t launch_oseen_tensor_batched(const double *pts, double *G, long long n
 hipError_t launch_stresslet_times_normal(const double *pts, const double *normals, double *G,
                                          long long n, double reg, double eps, hipStream_t stream);
 hipError_t run_fp64_peak(double *out_tflops);
+/* out[3]: cost of a v_rsq_f64 and of a broadcast ds_read_b128 in v_fma_f64
+ * issue slots, and the base run's TFLOP/s. */
+hipError_t run_issue_cost_probe(double *out);
 
 } // namespace skelly
 

@@ -20,10 +20,12 @@
  * slice. A fixed cost per WG was fitted too and came out as zero within the
  * noise (either sign at the two sizes swept), so the model has none.
  * Measured times follow ceil(W / n_cu) down to one WG a CU, for 1, 2 and 4
- * targets a thread, but a CU with fewer WGs than it holds at once
- * (wg_per_cu, from the occupancy query) hides a little less of the tile
+ * targets a thread, but a CU with fewer WGs than wg_per_cu (the functor's
+ * launch bound K::MIN_WAVES: what a CU held at once when this was fitted,
+ * with the sources still staged through LDS tiles) hid a little less of that
  * staging: c_fill = 1 + c_underfill * (wg_per_cu - q) / (wg_per_cu - 1) for
- * q < wg_per_cu, else 1 (3 % at one WG a CU, 1.5 % at two of three).
+ * q < wg_per_cu, else 1 (3 % at one WG a CU, 1.5 % at two of three). The
+ * constant has not been refitted since the sources moved to scalar loads.
  * Constants and what they were measured on: profiles/pair_balance.md.
  *
  * While a launch has no more WGs than CUs, ceil() is 1 and every further

@@ -385,4 +385,12 @@ int skelly_fp64_peak_tflops(double *out_tflops) {
     return 0;
 }
 
+int skelly_issue_cost_probe(double *out3) {
+    Context &c = ctx();
+    std::lock_guard<std::mutex> lock(c.mu);
+    CHK("issue_cost_probe", c.ensure_stream());
+    CHK("issue_cost_probe", skelly::run_issue_cost_probe(out3));
+    return 0;
+}
+
 } /* extern "C" */
