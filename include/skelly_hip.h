@@ -215,6 +215,15 @@ int skelly_fp64_peak_tflops(double *out_tflops);
  * 0 on success. */
 int skelly_issue_cost_probe(double *out3);
 
+/* The pair kernels' reciprocal square root, argument by argument: for each of
+ * the n doubles of d_x, d_seed gets the raw v_rsq_f64 and d_refined the
+ * refined R = 2/sqrt(x) that every functor and dense builder computes with
+ * (x == 0 gives inf and NaN, x == inf gives 0 and NaN: what the r == 0 mask
+ * relies on). Device pointers, async on `stream`, no synchronization.
+ * 0 on success. */
+int skelly_rsq_accuracy_probe(const double *d_x, double *d_seed, double *d_refined, long long n,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,7 @@ SIGNATURES = {
     "skelly_oseen_tensor_batched_device": (_I, [_PV, _PV, _LL, _LL, _D, _D, _D, _PV]),
     "skelly_fp64_peak_tflops": (_I, [_DP]),
     "skelly_issue_cost_probe": (_I, [_DP]),
+    "skelly_rsq_accuracy_probe": (_I, [_PV, _PV, _PV, _LL, _PV]),
 }
 for _name, _family in PAIR_FAMILY.items():
     SIGNATURES[f"skelly_{_name}_host"] = (_I, _PAIR_ARGS[_family](_DP))

@@ -115,8 +115,13 @@ __device__ inline double rsq_x2(double x) {
      * (profiles/rocprof_r01.md): identical norm-relative parity vs the CPU
      * oracle (~5e-16 at 2e4x4096 incl. near-coincident pairs) and
      * +4.6%/+2.9%/+2.2% on stokeslet/stresslet/oseen over the Householder
-     * form — v_rsq_f64's seed is accurate enough that one quadratic step
-     * reaches the fp64 rounding floor of the summation. */
+     * form. That parity is a property of sums over thousands of sources, not
+     * of a single pair: v_rsq_f64's seed is good to 5.2e-8 relative (2^-24.2,
+     * measured by skelly_rsq_accuracy_probe over 2^17 arguments,
+     * profiles/pair_accuracy.md), so R carries 1.5 e^2 = up to 36 u
+     * (4.0e-15, u = 2^-53) on top of the step's 2.5 u of rounding, and a
+     * term in R^p p times that. tests/pair_reference.py bounds it by
+     * E_RSQ = 1.5 (2 e)^2 + 2.5 u = 1.62e-14. */
     const double t = x * y;
     const double q = __builtin_fma(-t, y, 3.0);
     return y * q;
@@ -255,8 +260,9 @@ struct OseenContract : VelocityTraits {
      * applied once at the end (linear in the sum). With y = 2*fr and
      * g = rho/4: y^3 (d.g) = 2 gr (d.rho), so both terms are 2x.
      * Unmasked, a coincident pair would add the finite fr*rho, so the high
-     * dword of dr2 is min-tracked instead: 0 there means dr2 < 2^-1022
-     * (zero or subnormal) and sends the chunk to the masked rerun. */
+     * dword of dr2 is min-tracked instead: 0 there means dr2 < 2^-1042
+     * (the exponent field and the top 20 mantissa bits are zero: zero or a
+     * small subnormal) and sends the chunk to the masked rerun. */
     template <bool MASKED>
     __device__ static inline void pair(const double t[3], const double sp[3], const double rho[3],
                                        const double g[3], double acc[3], const Params &p,
@@ -1349,6 +1355,35 @@ hipError_t run_issue_cost_probe(double *out) {
     out[1] = (lds - base) / base * per;
     out[2] = 2.0 * PROBE_FMA * (double)PROBE_ITERS * blocks * 256 / (base * 1e-3) / 1e12;
     return hipSuccess;
+}
+
+/* ---- rsqrt accuracy probe (what the functors' one primitive returns) ----
+ * seed[i] = the raw v_rsq_f64 of x[i], refined[i] = rsq_x2(x[i]), the very
+ * function the functors and builders call. One thread an argument; measured
+ * against a long double 1/sqrt(x) in tests/test_gpu_rsq.py
+ * (profiles/pair_accuracy.md). */
+__global__ __launch_bounds__(BLOCK) void rsq_probe_kernel(const double *__restrict__ x,
+                                                          double *__restrict__ seed,
+                                                          double *__restrict__ refined,
+                                                          long long n) {
+    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n)
+        return;
+    const double xi = x[i];
+    double y;
+    asm("v_rsq_f64 %0, %1" : "=v"(y) : "v"(xi));
+    seed[i] = y;
+    refined[i] = rsq_x2(xi);
+}
+
+hipError_t launch_rsq_probe(const double *x, double *seed, double *refined, long long n,
+                            hipStream_t stream) {
+    if (n <= 0)
+        return hipSuccess;
+    const long long blocks = (n + BLOCK - 1) / BLOCK;
+    hipLaunchKernelGGL(rsq_probe_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, stream, x, seed,
+                       refined, n);
+    return hipGetLastError();
 }
 
 } // namespace skelly

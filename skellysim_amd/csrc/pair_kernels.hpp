@@ -45,6 +45,10 @@ hipError_t run_fp64_peak(double *out_tflops);
 /* out[3]: cost of a v_rsq_f64 and of a broadcast ds_read_b128 in v_fma_f64
  * issue slots, and the base run's TFLOP/s. */
 hipError_t run_issue_cost_probe(double *out);
+/* seed[i] = v_rsq_f64(x[i]), refined[i] = rsq_x2(x[i]) = 2/sqrt(x[i]) as the
+ * functors compute it; device pointers of n doubles each. */
+hipError_t launch_rsq_probe(const double *x, double *seed, double *refined, long long n,
+                            hipStream_t stream);
 
 } // namespace skelly
 

@@ -393,4 +393,11 @@ int skelly_issue_cost_probe(double *out3) {
     return 0;
 }
 
+int skelly_rsq_accuracy_probe(const double *d_x, double *d_seed, double *d_refined, long long n,
+                              void *stream) {
+    CHK("skelly_rsq_accuracy_probe",
+        skelly::launch_rsq_probe(d_x, d_seed, d_refined, n, (hipStream_t)stream));
+    return 0;
+}
+
 } /* extern "C" */

@@ -5,9 +5,13 @@ checked two ways: against the CPU oracle at the parity bar of
 test_gpu_parity.py, and fast path on against fast path off in the same build,
 which must agree bit for bit.
 
-Sizes are a few thousand points: TILE = 512 sources per LDS tile, CHUNK = 64
-sources per check, unroll 4, 256-thread blocks with up to 4 targets a thread
-(target i sits in slot (i % 1024) // 256, wave (i % 256) // 64)."""
+Sizes are a few thousand points: CHUNK = 64 sources per check, counted from
+the slice start and read from the packed records in groups of 2 sources (1
+for the stresslet), two groups in flight; 256-thread blocks with up to 4
+targets a thread (target i sits in slot (i % 1024) // 256, wave
+(i % 256) // 64). Where a case below speaks of tiles of 512 sources or of an
+unroll by 4, those are the boundaries of the earlier LDS-staged loop; the
+sizes are kept, they still leave a short last chunk and an odd last group."""
 
 import numpy as np
 import pytest
