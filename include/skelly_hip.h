@@ -24,7 +24,9 @@
  * (kernels.cu:9-15); this library instead returns nonzero error codes
  * (int-returning functions) and records a message retrievable via
  * skelly_hip_last_error(). The void reference-signature wrappers record the
- * error and leave u_trg untouched.
+ * error and leave u_trg untouched. A negative count is such an error in every
+ * entry point, found before any HIP call ("<entry point>: negative size"); a
+ * zero count is not one.
  *
  * Threading: calls are serialized by an internal mutex per the reference's
  * MPI_THREAD_FUNNELED usage (src/skelly_sim.cpp:14) — re-entrant per
@@ -43,13 +45,23 @@ extern "C" {
 
 /* ---- library / device management ---- */
 
-/* Force the persistent (grow-only hipMalloc) split-K workspace on/off at
- * runtime, overriding the SKELLY_PERSISTENT_WS env var (on=1/0; -1 not
- * accepted — call once). Required before hipGraph capture of launches
- * that take the split path: the async-mempool workspace cannot be
- * recorded, while the persistent one allocates only during uncaptured
- * warmup. */
+/* Where every pair launch, host and device forms alike, takes its workspace
+ * (source records and slice partials) from, overriding the SKELLY_PERSISTENT_WS
+ * env var (on=-1 follows it again): on=1 (default) a grow-only hipMalloc block
+ * kept per (device, stream), on=0 a hipMallocAsync/hipFreeAsync pair per
+ * launch. Leave it on:
+ * with the mempool workspace synchronised back-to-back calls of different
+ * kernels have returned wrong results ("Launch workspace"), and
+ * its allocations cannot be captured into a hipGraph, while the persistent
+ * block allocates only when a launch outgrows it (in uncaptured warmup). A
+ * block lives as long as its stream is in use by this library; the host
+ * forms' own is released by skelly_hip_shutdown(). */
 void skelly_set_persistent_ws(int on);
+
+/* Capacity in bytes of the persistent workspace block kept for `stream` on
+ * the current device, 0 if there is none, into *out_bytes. For tests and
+ * memory accounting. 0 on success. */
+int skelly_persistent_ws_bytes(void *stream, long long *out_bytes);
 
 /* Mode of the pair kernels' unmasked fast path, overriding the
  * SKELLY_PAIR_FASTPATH env var: 0 = off (every pair goes through the r==0
@@ -79,7 +91,8 @@ int skelly_hip_device_count(void);
 /* Select the device used by subsequent calls (default 0). 0 on success. */
 int skelly_hip_set_device(int device);
 
-/* Release all persistent device buffers and streams. 0 on success. */
+/* Release all persistent device buffers and streams, the host forms' launch
+ * workspace included. 0 on success; the next call sets everything up again. */
 int skelly_hip_shutdown(void);
 
 /* ---- reference drop-in entry points (include/kernels.hpp:17-20) ----

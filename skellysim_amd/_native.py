@@ -41,6 +41,7 @@ PAIR_FAMILY = {
 # every function of include/skelly_hip.h: name -> (restype, argtypes)
 SIGNATURES = {
     "skelly_set_persistent_ws": (None, [_I]),
+    "skelly_persistent_ws_bytes": (_I, [_PV, ctypes.POINTER(_LL)]),
     "skelly_set_pair_fastpath": (None, [_I]),
     "skelly_set_pair_slices": (None, [_I]),
     "skelly_hip_version": (ctypes.c_char_p, []),

@@ -864,40 +864,91 @@ struct Knob {
 };
 } // namespace
 
-/* Optional persistent launch workspace (SKELLY_PERSISTENT_WS=1; the source
- * records of every launch and the partials of the split ones): replaces
- * the per-launch hipMallocAsync/hipFreeAsync pair with a grow-only buffer
- * cached per stream. Reuse across launches is safe because launches on one
- * stream are ordered; outgrown blocks are RETIRED (never freed or reused —
- * queued work may still reference them; geometric growth bounds the leak at
- * ~2x the final size). Default OFF: the stream-ordered mempool path is the
- * round-1-validated behavior, and deep queues of outstanding async
- * alloc/free pairs are the prime suspect for the sync-cadence corruption
- * documented in gmres.py / DESIGN.md — flip this on to test that
- * hypothesis. */
-static Knob g_persistent_ws{"SKELLY_PERSISTENT_WS", 0, [](int v) { return v != 0 ? 1 : 0; }};
+/* The launch workspace (the source records of every launch and the partials
+ * of the split ones). SKELLY_PERSISTENT_WS / skelly_set_persistent_ws():
+ *   1 (default)  a grow-only hipMalloc block cached per (device, stream).
+ *      Reuse across launches is safe because launches on one stream are
+ *      ordered; an outgrown block is RETIRED, not freed or reused, for as
+ *      long as its stream lives (queued work and captured graphs may still
+ *      reference it; geometric growth bounds what is held at ~2x the final
+ *      size). Nothing is allocated by a launch that fits, so such launches
+ *      can be captured into a graph.
+ *   0  a hipMallocAsync/hipFreeAsync pair per launch on the stream-ordered
+ *      mempool. This was the default until it was found to give wrong
+ *      results; see WORKSPACE_DEFECT below. Kept as a switch for comparison
+ *      only. A launch also falls back to it if hipMalloc fails.
+ *
+ * WORKSPACE_DEFECT (open; DESIGN.md, "Launch workspace"): with the mempool
+ * workspace, a fresh process that made ten synchronised calls of different
+ * kernels back to back, host forms or device forms, got a wrong result in
+ * 15 of 48 runs on MI355X (every target off by about one far source's worth:
+ * some of the records the pair kernel read were not the ones pack_sources
+ * had just written). It takes the pool handing its memory back at
+ * hipStreamSynchronize (release threshold 0) and the next launch mapping
+ * memory anew: with the threshold at its maximum, or with the persistent
+ * block, none in 24 and none in 48. */
+static Knob g_persistent_ws{"SKELLY_PERSISTENT_WS", 1, [](int v) { return v != 0 ? 1 : 0; }};
+
+namespace {
+struct WsEntry {
+    void *ptr = nullptr;
+    size_t cap = 0;
+    std::vector<void *> retired;
+};
+struct WsCache {
+    std::mutex mu;
+    std::map<std::pair<int, hipStream_t>, WsEntry> blocks; /* (device, stream) */
+};
+WsCache &ws_cache() {
+    static WsCache c;
+    return c;
+}
+int current_device() {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    return dev;
+}
+} // namespace
 
 static double *persistent_ws(hipStream_t stream, size_t bytes) {
-    struct Entry {
-        void *ptr = nullptr;
-        size_t cap = 0;
-    };
-    static std::mutex mu;
-    static std::map<hipStream_t, Entry> cache;
-    static std::vector<void *> retired;
-    std::lock_guard<std::mutex> lk(mu);
-    Entry &e = cache[stream];
+    WsCache &c = ws_cache();
+    const int dev = current_device();
+    std::lock_guard<std::mutex> lk(c.mu);
+    WsEntry &e = c.blocks[{dev, stream}];
     if (e.cap < bytes) {
         size_t want = bytes * 2;
         void *p = nullptr;
         if (hipMalloc(&p, want) != hipSuccess)
             return nullptr; /* caller falls back to the async path */
         if (e.ptr)
-            retired.push_back(e.ptr);
+            e.retired.push_back(e.ptr);
         e.ptr = p;
         e.cap = want;
     }
     return static_cast<double *>(e.ptr);
+}
+
+long long persistent_ws_bytes(hipStream_t stream) {
+    WsCache &c = ws_cache();
+    const int dev = current_device();
+    std::lock_guard<std::mutex> lk(c.mu);
+    auto it = c.blocks.find({dev, stream});
+    return it == c.blocks.end() ? 0 : (long long)it->second.cap;
+}
+
+void release_persistent_ws(hipStream_t stream) {
+    WsCache &c = ws_cache();
+    std::lock_guard<std::mutex> lk(c.mu);
+    for (auto it = c.blocks.begin(); it != c.blocks.end();) {
+        if (it->first.second != stream) {
+            ++it;
+            continue;
+        }
+        (void)hipFree(it->second.ptr);
+        for (void *p : it->second.retired)
+            (void)hipFree(p);
+        it = c.blocks.erase(it);
+    }
 }
 
 /* Unmasked fast path of the pair kernels (see the file header). Mode, from
@@ -1395,6 +1446,11 @@ hipError_t launch_rsq_probe(const double *x, double *seed, double *refined, long
  * UNCAPTURED warmup pass, so capture itself allocates nothing. */
 extern "C" void skelly_set_persistent_ws(int on) {
     skelly::g_persistent_ws.forced = on;
+}
+
+extern "C" int skelly_persistent_ws_bytes(void *stream, long long *out_bytes) {
+    *out_bytes = skelly::persistent_ws_bytes((hipStream_t)stream);
+    return 0;
 }
 
 /* Runtime override of the unmasked pair fast path: 0 off, 1 auto, 2 always

@@ -36,6 +36,12 @@ hipError_t launch_pair_kernel(PairKernel kernel, const double *r_src, const doub
                               const double *r_trg, double *out, long long n_src, long long n_trg,
                               double scale, double reg, double eps, hipStream_t stream);
 
+/* The persistent launch workspace of `stream` on the current device: its
+ * capacity in bytes (0 without one), and its release with every block it
+ * retired, for a stream that is idle and about to be destroyed. */
+long long persistent_ws_bytes(hipStream_t stream);
+void release_persistent_ws(hipStream_t stream);
+
 /* Dense builders and the fp64 peak microbenchmark. */
 hipError_t launch_oseen_tensor_batched(const double *pts, double *G, long long nf, long long n,
                                        double eta, double reg, double eps, hipStream_t stream);

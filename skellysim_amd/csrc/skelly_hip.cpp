@@ -28,9 +28,21 @@ constexpr double kOneOver8Pi = 1.0 / 8.0 / M_PI; /* kernels.cu:59 */
 
 thread_local std::string g_last_error;
 
-void set_error(const char *where, hipError_t err) {
-    g_last_error = std::string(where) + ": " + hipGetErrorString(err);
+void set_error(const char *where, const char *what) {
+    g_last_error = std::string(where) + ": " + what;
     std::fprintf(stderr, "[skelly-hip] %s\n", g_last_error.c_str());
+}
+
+void set_error(const char *where, hipError_t err) { set_error(where, hipGetErrorString(err)); }
+
+/* The argument check every entry point makes before its first HIP call: a
+ * negative count is an error of the caller's (message recorded, -1), never a
+ * launch and never a buffer size. */
+bool negative_size(const char *where, long long a, long long b = 0) {
+    if (a >= 0 && b >= 0)
+        return false;
+    set_error(where, "negative size");
+    return true;
 }
 
 /* Persistent per-process device state. Calls are serialized (the reference is
@@ -85,6 +97,9 @@ struct Context {
         for (auto &c : cap)
             c = 0;
         if (stream_ready) {
+            /* the launch workspace cached for this stream goes with it */
+            (void)hipStreamSynchronize(stream);
+            skelly::release_persistent_ws(stream);
             (void)hipStreamDestroy(stream);
             stream_ready = false;
         }
@@ -111,6 +126,8 @@ Context &ctx() {
 int pair_device(const char *where, PairKernel kernel, const double *d_r_src,
                 const double *d_f_src, long long n_src, const double *d_r_trg, double *d_out,
                 long long n_trg, double scale, double reg, double eps, void *stream) {
+    if (negative_size(where, n_src, n_trg))
+        return -1;
     CHK(where, skelly::launch_pair_kernel(kernel, d_r_src, d_f_src, d_r_trg, d_out, n_src, n_trg,
                                           scale, reg, eps, (hipStream_t)stream));
     return 0;
@@ -122,10 +139,8 @@ int pair_device(const char *where, PairKernel kernel, const double *d_r_src,
 int pair_host(const char *where, PairKernel kernel, const double *r_src, const double *f_src,
               long long n_src, const double *r_trg, double *out, long long n_trg, double scale,
               double reg, double eps) {
-    if (n_src < 0 || n_trg < 0) {
-        g_last_error = std::string(where) + ": negative size";
+    if (negative_size(where, n_src, n_trg))
         return -1;
-    }
     if (n_trg == 0)
         return 0;
     const skelly::PairDims dims = skelly::pair_kernel_dims(kernel);
@@ -338,6 +353,8 @@ int skelly_rotlet_grad_device(const double *d_r_src, const double *d_r_trg,
 int skelly_stresslet_normal_density_host(const double *r_src, const double *normals,
                                          const double *density, double *out, long long n,
                                          double reg, double epsilon_distance) {
+    if (negative_size("skelly_stresslet_normal_density_host", n))
+        return -1;
     /* interleave [normal | density] into the (n, 6) source-strength array */
     std::vector<double> nd((size_t)n * 6);
     for (long long i = 0; i < n; ++i) {
@@ -362,6 +379,8 @@ int skelly_stresslet_normal_density_device(const double *d_r_src, const double *
 int skelly_stresslet_times_normal_device(const double *d_pts, const double *d_normals,
                                          double *d_out, long long n, double reg,
                                          double epsilon_distance, void *stream) {
+    if (negative_size("skelly_stresslet_times_normal_device", n))
+        return -1;
     CHK("skelly_stresslet_times_normal_device",
         skelly::launch_stresslet_times_normal(d_pts, d_normals, d_out, n, reg,
                                               epsilon_distance, (hipStream_t)stream));
@@ -371,6 +390,8 @@ int skelly_stresslet_times_normal_device(const double *d_pts, const double *d_no
 int skelly_oseen_tensor_batched_device(const double *d_pts, double *d_G, long long nf,
                                        long long n, double eta, double reg,
                                        double epsilon_distance, void *stream) {
+    if (negative_size("skelly_oseen_tensor_batched_device", nf, n))
+        return -1;
     CHK("skelly_oseen_tensor_batched_device",
         skelly::launch_oseen_tensor_batched(d_pts, d_G, nf, n, eta, reg, epsilon_distance,
                                             (hipStream_t)stream));

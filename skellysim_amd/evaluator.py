@@ -38,7 +38,6 @@ class _Pair:
     def __init__(self, symbol, srcdim, out):
         self.symbol, self.srcdim, self.out = symbol, srcdim, out
         self.host, self.device = f"skelly_{symbol}_host", f"skelly_{symbol}_device"
-        self.numel = math.prod(out)
         self.strength_first = _native.PAIR_FAMILY[symbol] == _native.STRENGTH
         # argument names for error messages
         self.names = ("r_src", "f_src" if self.strength_first else "density")
@@ -75,6 +74,13 @@ def _ptr(a):
     return a.ctypes.data_as(_DP)
 
 
+def _same_length(n, name, n_src, src_name):
+    """A per-source array has one row per source: the library reads n_src rows
+    of it, whatever it holds."""
+    if n != n_src:
+        raise ValueError(f"{name}: {n} rows for the {n_src} of {src_name}")
+
+
 def _pair_args(k, r_src, f_src, n_src, r_trg, out, n_trg):
     """The leading arguments in the order k's entry points take them."""
     if k.strength_first:
@@ -89,6 +95,7 @@ def _host_pair(k, r_src, f_src, r_trg, scalars, names=None):
     src = _rows(r_src, 3, names[0])
     f = _rows(f_src, k.srcdim, names[1])
     trg = _rows(r_trg, 3, "r_trg")
+    _same_length(len(f), names[1], len(src), names[0])
     out = np.zeros((len(trg),) + k.out)
     fn = getattr(_native.lib(), k.host)
     rc = fn(*_pair_args(k, _ptr(src), _ptr(f), len(src), _ptr(trg), _ptr(out), len(trg)),
@@ -177,6 +184,8 @@ def stresslet_times_normal_times_density(r_src, normals, density, reg=5e-3,
     src = _rows(r_src, 3, "r_src")
     nrm = _rows(normals, 3, "normals")
     rho = _rows(density, 3, "density")
+    _same_length(len(nrm), "normals", len(src), "r_src")
+    _same_length(len(rho), "density", len(src), "r_src")
     out = np.zeros((len(src), 3))
     rc = _native.lib().skelly_stresslet_normal_density_host(
         _ptr(src), _ptr(nrm), _ptr(rho), _ptr(out), len(src),
@@ -200,18 +209,23 @@ def _dev_rows(t, dim, name):
     return t.contiguous()
 
 
-def _dev_out(out, r_trg, shape, numel):
-    """The result tensor (n_trg,) + shape: a fresh one, or the caller's `out`
-    if the kernel can write it as is."""
+def _dev_result(out, shape, like):
+    """The result tensor of `shape`: a fresh one on `like`'s device, or the
+    caller's `out` if a kernel can write it as is."""
     import torch
-    n_trg = r_trg.shape[0]  # (len() of a tensor costs several times this)
     if out is None:
-        return torch.empty((n_trg,) + shape, dtype=torch.float64, device=r_trg.device)
+        return torch.empty(shape, dtype=torch.float64, device=like.device)
     if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64
-            and out.is_contiguous() and out.numel() == n_trg * numel):
+            and out.is_contiguous() and out.numel() == math.prod(shape)):
         raise ValueError("out: expected a contiguous float64 CUDA tensor of "
-                         f"(n_trg, {', '.join(map(str, shape))})")
+                         f"({', '.join(map(str, shape))})")
     return out
+
+
+def _dev_out(out, r_trg, shape):
+    """_dev_result for a pair kernel: (n_trg,) + shape."""
+    # (shape[0] of a tensor: len() costs several times this)
+    return _dev_result(out, (r_trg.shape[0],) + shape, r_trg)
 
 
 def _dptr(t):
@@ -229,7 +243,8 @@ def _device_pair(k, r_src, f_src, r_trg, out, scalars):
     r_src = _dev_rows(r_src, 3, "r_src")
     f_src = _dev_rows(f_src, k.srcdim, k.names[1])
     r_trg = _dev_rows(r_trg, 3, "r_trg")
-    out = _dev_out(out, r_trg, k.out, k.numel)
+    _same_length(f_src.shape[0], k.names[1], r_src.shape[0], "r_src")
+    out = _dev_out(out, r_trg, k.out)
     fn = getattr(_native.lib(), k.device)
     rc = fn(*_pair_args(k, _dptr(r_src), _dptr(f_src), r_src.shape[0], _dptr(r_trg), _dptr(out),
                         r_trg.shape[0]),
@@ -262,8 +277,10 @@ def stresslet_normal_density_device(r_src, normals, density, r_trg=None, reg=5e-
     normals = _dev_rows(normals, 3, "normals")
     density = _dev_rows(density, 3, "density")
     r_trg = r_src if r_trg is None else _dev_rows(r_trg, 3, "r_trg")
+    _same_length(len(normals), "normals", len(r_src), "r_src")
+    _same_length(len(density), "density", len(r_src), "r_src")
     nd = torch.cat([normals, density], dim=1).contiguous()
-    out = _dev_out(out, r_trg, (3,), 3)
+    out = _dev_out(out, r_trg, (3,))
     rc = _native.lib().skelly_stresslet_normal_density_device(
         _dptr(r_src), _dptr(nd), _dptr(r_trg), _dptr(out), len(r_src), len(r_trg),
         float(reg), float(epsilon_distance), _stream_ptr())
@@ -278,8 +295,8 @@ def stresslet_times_normal_device(pts, normals, reg=5e-3, epsilon_distance=1e-5,
     pts = _dev_rows(pts, 3, "pts")
     normals = _dev_rows(normals, 3, "normals")
     n = len(pts)
-    if out is None:
-        out = torch.empty((3 * n, 3 * n), dtype=torch.float64, device=pts.device)
+    _same_length(len(normals), "normals", n, "pts")
+    out = _dev_result(out, (3 * n, 3 * n), pts)
     rc = _native.lib().skelly_stresslet_times_normal_device(
         _dptr(pts), _dptr(normals), _dptr(out), n, float(reg), float(epsilon_distance),
         _stream_ptr())
@@ -297,8 +314,7 @@ def oseen_tensor_batched_device(pts, eta=1.0, reg=5e-3, epsilon_distance=1e-5, o
         raise TypeError("pts: expected (nf, n, 3) fp64 CUDA tensor")
     pts = pts.contiguous()
     nf, n = pts.shape[0], pts.shape[1]
-    if out is None:
-        out = torch.empty((nf, 3 * n, 3 * n), dtype=torch.float64, device=pts.device)
+    out = _dev_result(out, (nf, 3 * n, 3 * n), pts)
     rc = _native.lib().skelly_oseen_tensor_batched_device(
         _dptr(pts), _dptr(out), nf, n, float(eta), float(reg), float(epsilon_distance),
         _stream_ptr())

@@ -190,4 +190,4 @@ def test_short_launch_after_long_through_persistent_workspace(ska, oracle_mod, c
             u = run_case(ska, oracle_mod, kernel, *short, n_slices, ref)
             assert np.array_equal(u, fresh[n_slices])
     finally:
-        _native.lib().skelly_set_persistent_ws(0)
+        _native.lib().skelly_set_persistent_ws(-1)
