@@ -162,6 +162,38 @@ inline MatrixXd rotlet_grad(const CMatrixRef &r_src, const CMatrixRef &r_trg,
     return g;
 }
 
+/* Pressures of the stokeslet, stresslet and oseen fields above (no reference
+ * counterpart on the direct path): 1 x n_trg, prefactor 1/(4 pi), no eta (no
+ * pressure depends on it). The rotlet's pressure is zero. */
+inline MatrixXd stokeslet_pressure(const CMatrixRef &r_src, const CMatrixRef &r_trg,
+                                   const CMatrixRef &f_src) {
+    MatrixXd p(1, r_trg.size() / 3);
+    check_rc(skelly_stokeslet_pressure_host(r_src.ptr, f_src.ptr, r_src.size() / 3, r_trg.ptr,
+                                            p.data(), r_trg.size() / 3),
+             "stokeslet_pressure");
+    return p;
+}
+
+inline MatrixXd stresslet_pressure(const CMatrixRef &r_src, const CMatrixRef &r_trg,
+                                   const CMatrixRef &f_src) {
+    MatrixXd p(1, r_trg.size() / 3);
+    check_rc(skelly_stresslet_pressure_host(r_src.ptr, f_src.ptr, r_src.size() / 3, r_trg.ptr,
+                                            p.data(), r_trg.size() / 3),
+             "stresslet_pressure");
+    return p;
+}
+
+inline MatrixXd oseen_tensor_contract_pressure(const CMatrixRef &r_src, const CMatrixRef &r_trg,
+                                               const CMatrixRef &density, double reg = 5e-3,
+                                               double epsilon_distance = 1e-5) {
+    MatrixXd p(1, r_trg.size() / 3);
+    check_rc(skelly_oseen_contract_pressure_host(r_src.ptr, r_trg.ptr, density.ptr, p.data(),
+                                                 r_src.size() / 3, r_trg.size() / 3, reg,
+                                                 epsilon_distance),
+             "oseen_tensor_contract_pressure");
+    return p;
+}
+
 /* Mirror of the reference's string-keyed backend selection
  * (fiber_container_base.cpp:20-33, periphery.cpp:337-352): "HIP" is this
  * engine; the reference's "CPU"/"FMM" backends are out of scope. */

@@ -183,6 +183,43 @@ int skelly_rotlet_grad_device(const double *d_r_src, const double *d_r_trg,
                               long long n_src, long long n_trg,
                               double eta, double reg, double epsilon_distance, void *stream);
 
+/* ---- pressures ----
+ *
+ * The Stokes pressure p that belongs to the velocity entry points, so that
+ * the stress is sigma = -p I + eta (G + G^T) with G from the gradient forms.
+ * With d = t - s and y = 1/sqrt(den):
+ *   stokeslet        p = 1/(4 pi) sum (f.d) y^3,                 den = r^2
+ *   oseen_contract   the same expression with the velocity kernel's den
+ *                    (r^2 > eps^2 ? r^2 : r^2 + reg^2): the definition of the
+ *                    regularized branch
+ *   stresslet        p = 1/(4 pi) sum [ tr(S) y^3 - 3 (d^T S d) y^5 ],
+ *                    S_kl = f_src[9 s + 3 k + l],                den = r^2
+ * Coincident pairs (r == 0) contribute exactly 0. No pressure depends on eta,
+ * so these forms take none (a double layer's f_dl = 2 eta n (x) rho carries
+ * its own). The rotlet's pressure is zero: it has no entry point.
+ * p_trg is double[n_trg], overwritten. Argument order and error contract are
+ * those of the velocity forms without eta; the device forms are asynchronous
+ * on `stream`, perform no synchronization and use the persistent workspace.
+ * Results are bit-reproducible and independent of skelly_set_pair_fastpath. */
+int skelly_stokeslet_pressure_host(const double *r_src, const double *f_src, long long n_src,
+                                   const double *r_trg, double *p_trg, long long n_trg);
+int skelly_stresslet_pressure_host(const double *r_src, const double *f_src, long long n_src,
+                                   const double *r_trg, double *p_trg, long long n_trg);
+int skelly_oseen_contract_pressure_host(const double *r_src, const double *r_trg,
+                                        const double *density, double *p_trg,
+                                        long long n_src, long long n_trg,
+                                        double reg, double epsilon_distance);
+int skelly_stokeslet_pressure_device(const double *d_r_src, const double *d_f_src,
+                                     long long n_src, const double *d_r_trg, double *d_p_trg,
+                                     long long n_trg, void *stream);
+int skelly_stresslet_pressure_device(const double *d_r_src, const double *d_f_src,
+                                     long long n_src, const double *d_r_trg, double *d_p_trg,
+                                     long long n_trg, void *stream);
+int skelly_oseen_contract_pressure_device(const double *d_r_src, const double *d_r_trg,
+                                          const double *d_density, double *d_p_trg,
+                                          long long n_src, long long n_trg,
+                                          double reg, double epsilon_distance, void *stream);
+
 /* Contraction of the stresslet with a normal and a density field over one
  * point set (kernels::stresslet_times_normal_times_density,
  * src/core/kernels.cpp:307-334; no eta dependence, factor -3/(4*pi)):

@@ -34,6 +34,12 @@ from .evaluator import (  # noqa: F401
     stresslet_grad_device,
     oseen_contract_grad_device,
     rotlet_grad_device,
+    stokeslet_pressure,
+    stresslet_pressure,
+    oseen_contract_pressure,
+    stokeslet_pressure_device,
+    stresslet_pressure_device,
+    oseen_contract_pressure_device,
 )
 from .sharded import ShardedPairEvaluator, shard_sizes, allgather_rows  # noqa: F401
 

@@ -38,6 +38,38 @@ PAIR_FAMILY = {
     "oseen_contract_grad": DENSITY, "rotlet_grad": DENSITY,
 }
 
+
+class PressureCount(ctypes.c_longlong):
+    """The `long long` counts of the pressure entry points. A type of its own
+    keeps those entry points apart from the ones above wherever entry points
+    are enumerated by the type of their counts: tests/test_evaluator_arguments.py
+    lists the velocity and gradient forms that way, in sorted order and with its
+    cases numbered by position, and keeps exactly that list;
+    tests/test_pressure_cpu.py makes the same checks on the pressure forms."""
+
+
+# The pressures take the same two orders without eta (no pressure depends on it).
+STRENGTH_NO_ETA = "strength_no_eta"  # (r_src, f_src, n_src, r_trg, out, n_trg)
+DENSITY_NO_ETA = "density_no_eta"    # (r_src, r_trg, density, out, n_src, n_trg, reg, eps)
+_N = PressureCount
+_PRESSURE_ARGS = {
+    STRENGTH_NO_ETA: lambda p: [p, p, _N, p, p, _N],
+    DENSITY_NO_ETA: lambda p: [p, p, p, p, _N, _N, _D, _D],
+}
+# skelly_<name>_host and skelly_<name>_device exist for every key here too
+PRESSURE_FAMILY = {
+    "stokeslet_pressure": STRENGTH_NO_ETA, "stresslet_pressure": STRENGTH_NO_ETA,
+    "oseen_contract_pressure": DENSITY_NO_ETA,
+}
+
+
+def strength_first(symbol):
+    """Whether skelly_<symbol>_* take (r_src, f_src, n_src, r_trg, ...), the
+    strength orders, and not (r_src, r_trg, density, ...)."""
+    family = PAIR_FAMILY.get(symbol) or PRESSURE_FAMILY[symbol]
+    return family in (STRENGTH, STRENGTH_NO_ETA)
+
+
 # every function of include/skelly_hip.h: name -> (restype, argtypes)
 SIGNATURES = {
     "skelly_set_persistent_ws": (None, [_I]),
@@ -62,6 +94,9 @@ SIGNATURES = {
 for _name, _family in PAIR_FAMILY.items():
     SIGNATURES[f"skelly_{_name}_host"] = (_I, _PAIR_ARGS[_family](_DP))
     SIGNATURES[f"skelly_{_name}_device"] = (_I, _PAIR_ARGS[_family](_PV) + [_PV])
+for _name, _family in PRESSURE_FAMILY.items():
+    SIGNATURES[f"skelly_{_name}_host"] = (_I, _PRESSURE_ARGS[_family](_DP))
+    SIGNATURES[f"skelly_{_name}_device"] = (_I, _PRESSURE_ARGS[_family](_PV) + [_PV])
 
 
 def _bind(lib):

@@ -61,7 +61,8 @@
  *     the functor's launch bound, so the summation order stays reproducible;
  *     skelly_set_pair_slices() forces a count for sweeps and tests.
  *   - The same driver evaluates the analytic velocity gradients of the four
- *     kernels (9 outputs a target, K::OUTDIM; functors further down).
+ *     kernels (9 outputs a target, K::OUTDIM; functors further down) and
+ *     the pressures of the Stokeslet, Oseen and stresslet fields (1 output).
  *
  * Roofline: compute-bound on the fp64 VALU. The kernels are
  * deliberately not GEMM-shaped: gfx950's fp64 matrix rate equals its vector
@@ -578,6 +579,117 @@ struct RotletGrad : GradTraits {
         acc[6] = __builtin_fma(qz, dx, acc[6]) - wy;
         acc[7] = __builtin_fma(qz, dy, acc[7]) + wx;
         acc[8] = __builtin_fma(qz, dz, acc[8]);
+    }
+    __device__ static inline double finish(double a, const Params &p) { return a * p.scale; }
+};
+
+/* ---- pressure functors --------------------------------------------------
+ * The Stokes pressure p that goes with the velocity kernels above, one
+ * accumulator per target (OUTDIM 1); d = t - s, y = 1/sqrt(den), R = 2y.
+ * With sigma = -p I + eta (G + G^T) and the velocity's 1/(8 pi eta):
+ *   Stokeslet / Oseen   p = 1/(4 pi) sum (f.d) y^3
+ *   Stresslet           p = 1/(4 pi) sum [ tr(S) y^3 - 3 C y^5 ],  C = d^T S d
+ *   Rotlet              p = 0 identically: there is no functor.
+ * Neither depends on eta (a double layer's f_dl = 2 eta n (x) rho brings its
+ * own). Every pair goes through the r == 0 mask (FASTPATH off, as for the
+ * gradients), so the result cannot depend on skelly_set_pair_fastpath.
+ *
+ * MAX_TPT = 4, MIN_WAVES = 4. One accumulator a target needs 8 VGPRs a
+ * target (6 of coordinates, 2 of sum) against the velocity functors' 12, and
+ * the compiler's kernel-resource-usage reports 58 (StokesletPressure) and 66
+ * (StressletPressure) VGPRs at 4 targets a thread, 28 and 38 at one, no
+ * scratch: 8 targets would fit the register file. They are not taken: the
+ * loop is bound by fp64 VALU issue, not by the scalar record loads that more
+ * targets a thread would amortise (a source's 6 or 12 SGPR pairs already
+ * serve 4 x 64 pairs), and the launch planner and dispatch_tpt are built and
+ * fitted for 1, 2 and 4. The spare registers go to occupancy instead: a
+ * launch bound of 4 waves a SIMD (a 128-VGPR budget, met twice over), one
+ * more than the velocity functors, to cover the rsq latency of a loop with
+ * this little independent arithmetic a pair. SGPRs: two groups in flight,
+ * 2 x GROUP x 2 x (3 + SRCDIM) = 48 for both, 84-86 in all of the ~100. */
+
+struct PressureTraits {
+    static constexpr int OUTDIM = 1;
+    static constexpr int MAX_TPT = 4;
+    static constexpr int MIN_WAVES = 4;
+    static constexpr int AUXDIM = 0;
+    static constexpr bool HAS_MASK = true;
+    static constexpr bool FASTPATH = false;
+    static constexpr bool NAN_PROBE = false;
+    static constexpr double ACC_FOLD = 8.0; /* R^3 = 8 y^3 */
+};
+
+/* Stokeslet and regularized Oseen in one functor, as StokesletGrad:
+ * Params{., 0, 0} is the plain Stokeslet, else den follows OseenContract::pair
+ * (the pressure of the regularized branch is defined by the same
+ * substitution). acc += R^3 (f.d). */
+struct StokesletPressure : PressureTraits {
+    static constexpr int GROUP = SKELLY_GROUP;
+    static constexpr int SRCDIM = 3;
+    struct Params {
+        double scale; /* 1/(4*pi) / ACC_FOLD */
+        double reg2;
+        double eps2;
+    };
+    static Params make_params(double scale, double reg, double eps) {
+        return {scale, reg * reg, eps * eps};
+    }
+    template <bool MASKED>
+    __device__ static inline void pair(const double t[3], const double sp[3], const double f[3],
+                                       const double *, double acc[1], const Params &p,
+                                       unsigned &) {
+        const double dx = t[0] - sp[0];
+        const double dy = t[1] - sp[1];
+        const double dz = t[2] - sp[2];
+        double r2 = dx * dx;
+        r2 = __builtin_fma(dy, dy, r2);
+        r2 = __builtin_fma(dz, dz, r2);
+        const double den = (r2 > p.eps2) ? r2 : r2 + p.reg2;
+        double R = rsq_x2(den);
+        if (MASKED)
+            R = (r2 == 0.0) ? 0.0 : R;
+        const double R3 = (R * R) * R;
+        double fd = f[0] * dx;
+        fd = __builtin_fma(f[1], dy, fd);
+        fd = __builtin_fma(f[2], dz, fd);
+        acc[0] = __builtin_fma(fd, R3, acc[0]);
+    }
+    __device__ static inline double finish(double a, const Params &p) { return a * p.scale; }
+};
+
+/* acc += R^3 (tr(S) - 0.75 R^2 C) = 8 [ tr(S) y^3 - 3 C y^5 ]. */
+struct StressletPressure : PressureTraits {
+    static constexpr int GROUP = 1; /* 24 SGPRs a source */
+    static constexpr int SRCDIM = 9;
+    struct Params {
+        double scale; /* 1/(4*pi) / ACC_FOLD */
+    };
+    static Params make_params(double scale, double, double) { return {scale}; }
+    template <bool MASKED>
+    __device__ static inline void pair(const double t[3], const double sp[3], const double f[9],
+                                       const double *, double acc[1], const Params &,
+                                       unsigned &) {
+        const double dx = t[0] - sp[0];
+        const double dy = t[1] - sp[1];
+        const double dz = t[2] - sp[2];
+        const double dxx = dx * dx, dyy = dy * dy, dzz = dz * dz;
+        double dr2 = dxx + dyy;
+        dr2 += dzz;
+        double R = rsq_x2(dr2);
+        if (MASKED)
+            R = (dr2 == 0.0) ? 0.0 : R;
+        const double R2 = R * R;
+        const double R3 = R2 * R;
+        /* C as Stresslet::pair's coeff */
+        double C = f[0] * dxx;
+        C = __builtin_fma(f[4], dyy, C);
+        C = __builtin_fma(f[8], dzz, C);
+        C = __builtin_fma(f[1] + f[3], dx * dy, C);
+        C = __builtin_fma(f[2] + f[6], dx * dz, C);
+        C = __builtin_fma(f[5] + f[7], dy * dz, C);
+        const double tr = (f[0] + f[4]) + f[8];
+        const double q = __builtin_fma(-0.75 * R2, C, tr);
+        acc[0] = __builtin_fma(R3, q, acc[0]);
     }
     __device__ static inline double finish(double a, const Params &p) { return a * p.scale; }
 };
@@ -1112,6 +1224,10 @@ static auto with_kernel(PairKernel kernel, F &&f) {
         return f(StressletGrad{});
     case PairKernel::RotletGrad:
         return f(RotletGrad{});
+    case PairKernel::StokesletPressure:
+        return f(StokesletPressure{});
+    case PairKernel::StressletPressure:
+        return f(StressletPressure{});
     }
     __builtin_unreachable();
 }

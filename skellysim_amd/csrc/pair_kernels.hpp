@@ -19,6 +19,8 @@ enum class PairKernel {
     StokesletGrad, /* also the regularized Oseen gradient (reg, eps != 0) */
     StressletGrad,
     RotletGrad,
+    StokesletPressure, /* also the regularized Oseen pressure (reg, eps != 0) */
+    StressletPressure,
 };
 
 /* Doubles per source of the strength array and per target of the output

@@ -25,6 +25,7 @@ using skelly::PairKernel;
 namespace {
 
 constexpr double kOneOver8Pi = 1.0 / 8.0 / M_PI; /* kernels.cu:59 */
+constexpr double kOneOver4Pi = 1.0 / (4.0 * M_PI); /* the pressures' prefactor */
 
 thread_local std::string g_last_error;
 
@@ -135,7 +136,7 @@ int pair_device(const char *where, PairKernel kernel, const double *d_r_src,
 
 /* Host-pointer form: upload, launch, download, sync on the library's stream.
  * The kernel's own widths size the buffers (doubles per source of f_src, per
- * target of out: 3 velocity components, 9 of a gradient). */
+ * target of out: 3 velocity components, 9 of a gradient, 1 pressure). */
 int pair_host(const char *where, PairKernel kernel, const double *r_src, const double *f_src,
               long long n_src, const double *r_trg, double *out, long long n_trg, double scale,
               double reg, double eps) {
@@ -345,6 +346,52 @@ int skelly_rotlet_grad_device(const double *d_r_src, const double *d_r_trg,
     return pair_device("skelly_rotlet_grad_device", PairKernel::RotletGrad, d_r_src, d_density,
                        n_src, d_r_trg, d_g_trg, n_trg, scale_oseen(eta), reg, epsilon_distance,
                        stream);
+}
+
+/* ---- pressures: 1 double per target, prefactor 1/(4*pi), no eta ----
+ * The oseen forms run StokesletPressure with the regularization switched on;
+ * the rotlet's pressure is zero and has no entry point. */
+
+int skelly_stokeslet_pressure_host(const double *r_src, const double *f_src, long long n_src,
+                                   const double *r_trg, double *p_trg, long long n_trg) {
+    return pair_host("skelly_stokeslet_pressure_host", PairKernel::StokesletPressure, r_src,
+                     f_src, n_src, r_trg, p_trg, n_trg, kOneOver4Pi, 0.0, 0.0);
+}
+
+int skelly_stresslet_pressure_host(const double *r_src, const double *f_src, long long n_src,
+                                   const double *r_trg, double *p_trg, long long n_trg) {
+    return pair_host("skelly_stresslet_pressure_host", PairKernel::StressletPressure, r_src,
+                     f_src, n_src, r_trg, p_trg, n_trg, kOneOver4Pi, 0.0, 0.0);
+}
+
+int skelly_oseen_contract_pressure_host(const double *r_src, const double *r_trg,
+                                        const double *density, double *p_trg, long long n_src,
+                                        long long n_trg, double reg, double epsilon_distance) {
+    return pair_host("skelly_oseen_contract_pressure_host", PairKernel::StokesletPressure, r_src,
+                     density, n_src, r_trg, p_trg, n_trg, kOneOver4Pi, reg, epsilon_distance);
+}
+
+int skelly_stokeslet_pressure_device(const double *d_r_src, const double *d_f_src,
+                                     long long n_src, const double *d_r_trg, double *d_p_trg,
+                                     long long n_trg, void *stream) {
+    return pair_device("skelly_stokeslet_pressure_device", PairKernel::StokesletPressure, d_r_src,
+                       d_f_src, n_src, d_r_trg, d_p_trg, n_trg, kOneOver4Pi, 0.0, 0.0, stream);
+}
+
+int skelly_stresslet_pressure_device(const double *d_r_src, const double *d_f_src,
+                                     long long n_src, const double *d_r_trg, double *d_p_trg,
+                                     long long n_trg, void *stream) {
+    return pair_device("skelly_stresslet_pressure_device", PairKernel::StressletPressure, d_r_src,
+                       d_f_src, n_src, d_r_trg, d_p_trg, n_trg, kOneOver4Pi, 0.0, 0.0, stream);
+}
+
+int skelly_oseen_contract_pressure_device(const double *d_r_src, const double *d_r_trg,
+                                          const double *d_density, double *d_p_trg,
+                                          long long n_src, long long n_trg, double reg,
+                                          double epsilon_distance, void *stream) {
+    return pair_device("skelly_oseen_contract_pressure_device", PairKernel::StokesletPressure,
+                       d_r_src, d_density, n_src, d_r_trg, d_p_trg, n_trg, kOneOver4Pi, reg,
+                       epsilon_distance, stream);
 }
 
 /* stresslet x normal x density: the prefactor -3/(4*pi) is the functor's own

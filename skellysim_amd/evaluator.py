@@ -31,14 +31,14 @@ _DP = ctypes.POINTER(ctypes.c_double)
 class _Pair:
     """One pair kernel as this module sees it: the entry points
     skelly_<symbol>_host / skelly_<symbol>_device (argument order:
-    _native.PAIR_FAMILY), the doubles per source of its strength array and the
-    per-target shape of its result. `symbol` is also the _native.check label.
+    _native.PAIR_FAMILY / PRESSURE_FAMILY), the doubles per source of its
+    strength array and the per-target shape of its result. `symbol` is also the _native.check label.
     Everything a call needs is worked out here, once."""
 
     def __init__(self, symbol, srcdim, out):
         self.symbol, self.srcdim, self.out = symbol, srcdim, out
         self.host, self.device = f"skelly_{symbol}_host", f"skelly_{symbol}_device"
-        self.strength_first = _native.PAIR_FAMILY[symbol] == _native.STRENGTH
+        self.strength_first = _native.strength_first(symbol)
         # argument names for error messages
         self.names = ("r_src", "f_src" if self.strength_first else "density")
 
@@ -51,6 +51,9 @@ _STOKESLET_GRAD = _Pair("stokeslet_grad", 3, (3, 3))
 _STRESSLET_GRAD = _Pair("stresslet_grad", 9, (3, 3))
 _OSEEN_GRAD = _Pair("oseen_contract_grad", 3, (3, 3))
 _ROTLET_GRAD = _Pair("rotlet_grad", 3, (3, 3))
+_STOKESLET_PRESSURE = _Pair("stokeslet_pressure", 3, ())
+_STRESSLET_PRESSURE = _Pair("stresslet_pressure", 9, ())
+_OSEEN_PRESSURE = _Pair("oseen_contract_pressure", 3, ())
 
 
 def _rows(a, dim, name):
@@ -149,6 +152,28 @@ def oseen_contract_grad(r_src, r_trg, density, eta=1.0, reg=5e-3, epsilon_distan
 def rotlet_grad(r_src, r_trg, density, eta=1.0, reg=5e-3, epsilon_distance=1e-5):
     """Gradient of rotlet_gpu's field."""
     return _host_pair(_ROTLET_GRAD, r_src, density, r_trg, (eta, reg, epsilon_distance))
+
+
+# Pressures, host arrays: (n_trg,), the Stokes pressure that goes with the
+# velocity of the same sources (prefactor 1/(4 pi); no eta: no pressure depends
+# on it). sigma = -p I + eta (G + G^T) with G from the gradient forms. The
+# rotlet's pressure is identically zero, so it has no function here.
+
+def stokeslet_pressure(r_src, f_src, r_trg):
+    """p = 1/(4 pi) sum (f.d) / r^3 of stokeslet_direct_gpu's field, d = t - s."""
+    return _host_pair(_STOKESLET_PRESSURE, r_src, f_src, r_trg, ())
+
+
+def stresslet_pressure(r_src, f_src, r_trg):
+    """p = 1/(4 pi) sum [tr(S) / r^3 - 3 (d^T S d) / r^5] of
+    stresslet_direct_gpu's field, S_kl = f_src[:, 3k + l]."""
+    return _host_pair(_STRESSLET_PRESSURE, r_src, f_src, r_trg, ())
+
+
+def oseen_contract_pressure(r_src, r_trg, density, reg=5e-3, epsilon_distance=1e-5):
+    """Pressure of oseen_contract_direct_gpu's field: the Stokeslet's
+    expression with that kernel's regularized distance."""
+    return _host_pair(_OSEEN_PRESSURE, r_src, density, r_trg, (reg, epsilon_distance))
 
 
 class Evaluator:
@@ -350,3 +375,23 @@ def rotlet_grad_device(r_src, r_trg, density, eta=1.0, reg=5e-3, epsilon_distanc
                        out=None):
     """Gradient of rotlet_device's field."""
     return _device_pair(_ROTLET_GRAD, r_src, density, r_trg, out, (eta, reg, epsilon_distance))
+
+
+# ---------------------------------------------------------------------------
+# pressures on device tensors: (n_trg,); no eta (see the host forms)
+# ---------------------------------------------------------------------------
+
+def stokeslet_pressure_device(r_src, f_src, r_trg, out=None):
+    """Pressure of stokeslet_device's field. Async on torch's current stream."""
+    return _device_pair(_STOKESLET_PRESSURE, r_src, f_src, r_trg, out, ())
+
+
+def stresslet_pressure_device(r_src, f_src, r_trg, out=None):
+    """Pressure of stresslet_device's field."""
+    return _device_pair(_STRESSLET_PRESSURE, r_src, f_src, r_trg, out, ())
+
+
+def oseen_contract_pressure_device(r_src, r_trg, density, reg=5e-3, epsilon_distance=1e-5,
+                                   out=None):
+    """Pressure of oseen_contract_device's field."""
+    return _device_pair(_OSEEN_PRESSURE, r_src, density, r_trg, out, (reg, epsilon_distance))

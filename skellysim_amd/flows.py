@@ -22,7 +22,10 @@ Mirrors:
 The `*_flow_grad` / velocity_gradient_at_targets forms return the analytic
 velocity gradient G[t, i, j] = du_i/dx_j of the same fields (no reference
 counterpart: the reference differences the velocity), with
-vorticity_from_gradient / strain_rate_from_gradient on top.
+vorticity_from_gradient / strain_rate_from_gradient on top. The
+`*_flow_pressure` / pressure_at_targets forms return the pressure of the same
+fields, stress_at_targets the stress sigma = -p I + eta (G + G^T), and
+traction / surface_force_torque what a surface carries.
 
 All tensors are torch fp64; the pair-kernel legs require CUDA tensors (the
 product path; no CPU fallback).
@@ -200,6 +203,136 @@ def strain_rate_from_gradient(G):
         return 0.5 * (G + G.transpose(-1, -2))
     import numpy as np
     return 0.5 * (G + np.swapaxes(G, -1, -2))
+
+
+# ---------------------------------------------------------------------------
+# Pressure and stress. p is the Stokes pressure of the same fields (prefactor
+# 1/(4 pi), no eta dependence of its own; a rotlet's is zero), the stress is
+# sigma = -p I + eta (G + G^T) from p and the gradient kernels: two passes.
+# The pair kernels are reached through a system_fd backend's methods:
+# `backend=None` is HipBackend on r_trg's device (tensors in, tensors out, no
+# synchronization); any object with the same methods on numpy arrays serves
+# numpy inputs (the tests' closed forms).
+# ---------------------------------------------------------------------------
+
+def _compute(backend, r_trg):
+    if backend is not None:
+        return backend
+    from .system_fd import HipBackend
+    return HipBackend(r_trg.device)
+
+
+def _zero_rows(r_trg, *shape):
+    if torch.is_tensor(r_trg):
+        return torch.zeros((r_trg.shape[0],) + shape, dtype=r_trg.dtype, device=r_trg.device)
+    import numpy as np
+    return np.zeros((r_trg.shape[0],) + shape)
+
+
+def periphery_flow_pressure(node_pos, node_normal, density, r_trg, eta, backend=None):
+    """Pressure (n_trg,) of periphery_flow's field: the same
+    f_dl = 2*eta*n (x) density through the stresslet pressure kernel."""
+    if node_pos.shape[0] == 0:
+        return _zero_rows(r_trg)
+    return _compute(backend, r_trg).stresslet_normal_density_pressure(
+        node_pos, node_normal, density, r_trg, eta)
+
+
+def fiber_flow_pressure(r_src, fib_forces, weights, r_trg, backend=None):
+    """Pressure of fiber_flow's field without the self term (as
+    fiber_flow_grad)."""
+    if r_src.shape[0] == 0:
+        return _zero_rows(r_trg)
+    wf = fib_forces * weights[:, None]
+    return _compute(backend, r_trg).stokeslet_pressure(r_src, wf, r_trg)
+
+
+def body_flow_pressure(node_pos, node_normals, densities, centers, forces, torques, r_trg, eta,
+                       backend=None):
+    """Pressure of body_flow's field, term by term; the rotlet of the
+    torques has none."""
+    p = periphery_flow_pressure(node_pos, node_normals, densities, r_trg, eta, backend)
+    if centers.shape[0]:
+        p = p + _compute(backend, r_trg).stokeslet_pressure(centers, forces, r_trg)
+    return p
+
+
+def pressure_at_targets(r_trg, eta, fiber=None, shell=None, bodies=None, backend=None):
+    """Pressure (n_trg,) of velocity_at_targets' field, same dict inputs; the
+    fiber self term is never subtracted."""
+    p = _zero_rows(r_trg)
+    if fiber is not None:
+        p = p + fiber_flow_pressure(fiber["r_src"], fiber["forces"], fiber["weights"], r_trg,
+                                    backend)
+    if shell is not None:
+        p = p + periphery_flow_pressure(shell["node_pos"], shell["node_normal"],
+                                        shell["density"], r_trg, eta, backend)
+    if bodies is not None:
+        p = p + body_flow_pressure(bodies["node_pos"], bodies["node_normals"],
+                                   bodies["densities"], bodies["centers"], bodies["forces"],
+                                   bodies["torques"], r_trg, eta, backend)
+    return p
+
+
+def _gradient_through(backend, r_trg, eta, fiber, shell, bodies):
+    """velocity_gradient_at_targets' sum through a backend's `_grad` methods."""
+    g = _zero_rows(r_trg, 3, 3)
+    if fiber is not None and fiber["r_src"].shape[0]:
+        g = g + backend.stokeslet_grad(fiber["r_src"],
+                                       fiber["forces"] * fiber["weights"][:, None], r_trg, eta)
+    if shell is not None and shell["node_pos"].shape[0]:
+        g = g + backend.stresslet_normal_density_grad(
+            shell["node_pos"], shell["node_normal"], shell["density"], r_trg, eta)
+    if bodies is not None:
+        if bodies["node_pos"].shape[0]:
+            g = g + backend.stresslet_normal_density_grad(
+                bodies["node_pos"], bodies["node_normals"], bodies["densities"], r_trg, eta)
+        if bodies["centers"].shape[0]:
+            g = g + backend.stokeslet_grad(bodies["centers"], bodies["forces"], r_trg, eta)
+            g = g + backend.rotlet_grad(bodies["centers"], bodies["torques"], r_trg, eta)
+    return g
+
+
+def stress_from_fields(p, G, eta):
+    """sigma (n, 3, 3) = -p I + eta (G + G^T) from the pressure (n,) and the
+    velocity gradient (n, 3, 3); torch or numpy."""
+    if torch.is_tensor(G):
+        eye = torch.eye(3, dtype=G.dtype, device=G.device)
+        return eta * (G + G.transpose(-1, -2)) - p[..., None, None] * eye
+    import numpy as np
+    return eta * (G + np.swapaxes(G, -1, -2)) - np.asarray(p)[..., None, None] * np.eye(3)
+
+
+def stress_at_targets(r_trg, eta, fiber=None, shell=None, bodies=None, backend=None):
+    """Stress (n_trg, 3, 3) of velocity_at_targets' field: pressure_at_targets
+    and the velocity gradient of the same sources through stress_from_fields."""
+    backend = _compute(backend, r_trg)
+    G = _gradient_through(backend, r_trg, eta, fiber, shell, bodies)
+    p = pressure_at_targets(r_trg, eta, fiber=fiber, shell=shell, bodies=bodies,
+                            backend=backend)
+    return stress_from_fields(p, G, eta)
+
+
+def traction(stress, normals):
+    """sigma . n (n, 3): the force per area that the fluid on the side the
+    normal points to exerts across the surface element."""
+    if torch.is_tensor(stress):
+        return torch.einsum("nij,nj->ni", stress, normals)
+    import numpy as np
+    return np.einsum("nij,nj->ni", stress, normals)
+
+
+def surface_force_torque(points, normals, weights, stress, origin):
+    """(F, T): the quadrature sum_k w_k (sigma . n)_k and
+    sum_k w_k (x_k - origin) x (sigma . n)_k over a surface given by its
+    points (n, 3), normals (n, 3) and quadrature weights (n,)."""
+    wt = traction(stress, normals) * weights[:, None]
+    if torch.is_tensor(wt):
+        arm = points - torch.as_tensor(origin, dtype=points.dtype, device=points.device)
+        return wt.sum(dim=0), torch.linalg.cross(arm, wt).sum(dim=0)
+    import numpy as np
+    arm = points - np.asarray(origin, float)
+    return wt.sum(axis=0), np.cross(arm, wt).sum(axis=0)
 
 
 class ShellOperator:

@@ -24,12 +24,15 @@ the central-difference curl of the velocity field (streamline.cpp:16-35,
 115-165), with the singularity stop still on the VELOCITY norm
 (streamline.cpp:51, same observer for both line kinds).
 
-Two extension keys, which the reference client never sends and without
+Extension keys, which the reference client never sends and without
 which every response is unchanged: `"analytic": true` in the `vortexlines`
 map integrates the analytic curl (velocity_gradient_field, one gradient
-evaluation per point instead of six velocity probes), and a
+evaluation per point instead of six velocity probes), a
 `"velocity_gradient": {"x": ...}` entry adds a 9 x n `velocity_gradient`
-block (column t = row-major du_i/dx_j at target t) to the response."""
+block (column t = row-major du_i/dx_j at target t) to the response, a
+`"pressure": {"x": ...}` entry a 1 x n `pressure` block (pressure_field) and
+a `"stress": {"x": ...}` entry a 9 x n `stress` block (stress_field, column
+t = row-major sigma_ij at target t)."""
 
 import argparse
 import os
@@ -61,6 +64,12 @@ def eigen_encode_9xn(g):
     """(n, 3, 3) -> ['__eigen__', 9, n, colmajor]: column t is G[t] row-major."""
     g = np.asarray(g, dtype=np.float64).reshape(-1, 9)
     return ["__eigen__", 9, len(g), *g.reshape(-1).tolist()]
+
+
+def eigen_encode_1xn(p):
+    """(n,) -> ['__eigen__', 1, n, values]."""
+    p = np.asarray(p, dtype=np.float64).reshape(-1)
+    return ["__eigen__", 1, len(p), *p.tolist()]
 
 
 def eigen_encode_3xn(a):
@@ -265,6 +274,63 @@ def velocity_gradient_field(frame, targets, eta, compute, shell_geometry=None,
     return G
 
 
+def _inside_any_body(targets, bodies):
+    inside = np.zeros(len(targets), bool)
+    for b in bodies:
+        inside |= np.linalg.norm(targets - b.position[None, :], axis=1) < b.radius
+    return inside
+
+
+def pressure_field(frame, targets, eta, compute, shell_geometry=None,
+                   body_geometry=None, sources=None):
+    """Pressure (n,) of velocity_field: the same terms from the same sources,
+    each through the backend's `_pressure` method (the rotlets of the body
+    torques and of the point torques have none, the background flow is linear
+    and has a constant one, taken as 0). Inside a body the motion is rigid:
+    the fluid stress is 0 there and p is defined as 0."""
+    targets = np.asarray(targets, float).reshape(-1, 3)
+    p = np.zeros(len(targets))
+    if sources is not None:
+        psc, bs = sources
+        if psc is not None:
+            p += psc.flow_pressure(targets, float(frame.get("time", 0.0)), compute)
+        if bs is not None and bs.is_active():
+            p += bs.flow_pressure(targets)
+    fibers = fibers_from_frame(frame, eta)
+    if fibers:
+        r_src, wf = _fiber_sources(fibers)
+        p += compute.stokeslet_pressure(r_src, wf, targets)
+    dens = _shell_density(frame, shell_geometry)
+    if dens is not None:
+        p += compute.stresslet_normal_density_pressure(
+            shell_geometry["nodes"], shell_geometry["normals"], dens,
+            targets, eta)
+    bodies = bodies_from_frame(frame, body_geometry) \
+        if body_geometry is not None else []
+    if bodies:
+        nodes, normals, dens, centers, ft = _body_sources(fibers, bodies)
+        p += compute.stresslet_normal_density_pressure(nodes, normals, dens, targets, eta)
+        p += compute.stokeslet_pressure(centers, ft[:, 0:3], targets)
+        p[_inside_any_body(targets, bodies)] = 0.0
+    return p
+
+
+def stress_field(frame, targets, eta, compute, shell_geometry=None,
+                 body_geometry=None, sources=None):
+    """Stress (n, 3, 3) of velocity_field, sigma = -p I + eta (G + G^T) from
+    pressure_field and velocity_gradient_field. Inside a body the motion is
+    rigid (G antisymmetric, p = 0): sigma = 0 there."""
+    from .flows import stress_from_fields
+    targets = np.asarray(targets, float).reshape(-1, 3)
+    args = (frame, targets, eta, compute, shell_geometry, body_geometry, sources)
+    sigma = stress_from_fields(pressure_field(*args), velocity_gradient_field(*args), eta)
+    bodies = bodies_from_frame(frame, body_geometry) \
+        if body_geometry is not None else []
+    if bodies:
+        sigma[_inside_any_body(targets, bodies)] = 0.0
+    return sigma
+
+
 def vorticity(field_fn, pts, eps=1e-7):
     """Central-difference curl of the velocity field at each row of pts
     (get_vorticity_at_point, streamline.cpp:16-35: eps=1e-7, 6 evals/point;
@@ -421,6 +487,17 @@ def serve(stdin, stdout, traj, compute, eta=1.0, shell_geometry=None,
                 velocity_gradient_field(frame, xg, eta, compute, shell_geometry,
                                         body_geometry, sources)
                 if len(xg) else np.zeros((0, 3, 3)))
+        for key, field, encode, empty in (
+                ("pressure", pressure_field, eigen_encode_1xn, np.zeros(0)),
+                ("stress", stress_field, eigen_encode_9xn, np.zeros((0, 3, 3)))):
+            req = cmd.get(key)
+            if req:
+                xq = eigen_decode(req.get("x", []))
+                xq = np.asarray(xq, float).reshape(-1, 3) if np.size(xq) \
+                    else np.zeros((0, 3))
+                response[key] = encode(
+                    field(frame, xq, eta, compute, shell_geometry, body_geometry, sources)
+                    if len(xq) else empty)
         out = msgpack.packb(response)
         stdout.write(struct.pack("<Q", len(out)))
         stdout.write(out)

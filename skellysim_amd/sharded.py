@@ -150,6 +150,10 @@ class ShardedPairEvaluator:
                 compute_fn = lambda r, f, t, eta: ev.oseen_contract_device(r, t, f, eta)
             elif kernel == "rotlet":
                 compute_fn = lambda r, f, t, eta: ev.rotlet_device(r, t, f, eta)
+            elif kernel == "stokeslet_pressure":  # (n_trg,); no pressure reads eta
+                compute_fn = lambda r, f, t, eta: ev.stokeslet_pressure_device(r, f, t)
+            elif kernel == "stresslet_pressure":
+                compute_fn = lambda r, f, t, eta: ev.stresslet_pressure_device(r, f, t)
             else:
                 raise ValueError(f"unknown kernel {kernel!r}")
 

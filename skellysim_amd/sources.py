@@ -73,6 +73,19 @@ class PointSourceContainer:
                 np.stack([p.torque for p in torquers]), r_trg, eta)
         return grad
 
+    def flow_pressure(self, r_trg, time, backend):
+        """Pressure (n_trg,) of flow(): same liveness rules; the forces
+        through the backend's oseen_contract_pressure, the torques add
+        nothing (a rotlet's pressure is zero). No eta: no pressure reads it."""
+        r_trg = np.asarray(r_trg, float)
+        forcers = [p for p in self.points
+                   if not (p.time_to_live and time >= p.time_to_live) and p.force.any()]
+        if not forcers:
+            return np.zeros(len(r_trg))
+        return np.asarray(backend.oseen_contract_pressure(
+            np.stack([p.position for p in forcers]), r_trg,
+            np.stack([p.force for p in forcers])), float)
+
 
 class BackgroundSource:
     """background_source.cpp:14-22: v_j(r) = uniform_j +
@@ -105,3 +118,8 @@ class BackgroundSource:
         G = np.zeros((3, 3))
         G[np.arange(3), self.components] = self.scale_factor
         return np.broadcast_to(G, (len(np.asarray(r_trg, float).reshape(-1, 3)), 3, 3)).copy()
+
+    def flow_pressure(self, r_trg):
+        """Pressure (n_trg,) of flow(): zeros. A linear velocity field has no
+        Laplacian, so the Stokes pressure is constant, taken as 0."""
+        return np.zeros(len(np.asarray(r_trg, float).reshape(-1, 3)))

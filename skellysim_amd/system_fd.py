@@ -107,6 +107,20 @@ class HipBackend:
     def oseen_contract_grad(self, r_src, r_trg, density, eta):
         return self._eval("oseen_contract_grad", (r_src, r_trg, density), eta)
 
+    # pressures: (n_trg,), prefactor 1/(4 pi); the rotlet's is zero (no method)
+
+    def stokeslet_pressure(self, r_src, f_src, r_trg):
+        return self._eval("stokeslet_pressure", (r_src, f_src, r_trg))
+
+    def stresslet_normal_density_pressure(self, r_src, normals, density, r_trg, eta):
+        """Pressure of stresslet_normal_density's field (same f_dl, which is
+        where eta comes in)."""
+        return self._eval("stresslet_pressure",
+                          (r_src, self._f_dl(normals, density, eta), r_trg))
+
+    def oseen_contract_pressure(self, r_src, r_trg, density):
+        return self._eval("oseen_contract_pressure", (r_src, r_trg, density))
+
     def stresslet_times_normal(self, nodes, normals, eta):
         """Dense (3n, 3n) operator (kernels.cpp:264-287; eta-independent
         factor) — the M block of the body preconditioner."""
