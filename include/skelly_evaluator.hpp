@@ -194,6 +194,76 @@ inline MatrixXd oseen_tensor_contract_pressure(const CMatrixRef &r_src, const CM
     return p;
 }
 
+/* Streamlines (mirror of StreamLine::compute, streamline.cpp:67-113, for all
+ * seeds in one kernel launch; skelly_trace_streamlines_host). The field is the
+ * sum of the four source sets of StreamlineField, each possibly empty, plus
+ * the background and the rigid motion inside bodies. */
+struct StreamlineField {
+    CMatrixRef r_sl, f_sl;     /* Stokeslets: 3 x n, 3 x n */
+    CMatrixRef r_dl, f_dl;     /* stresslets: 3 x n, 9 x n */
+    CMatrixRef r_rot, torques; /* rotlets: 3 x n, 3 x n */
+    CMatrixRef r_os, f_os;     /* regularized Stokeslets: 3 x n, 3 x n */
+    bool has_background = false;
+    double uniform[3] = {0, 0, 0}, scale_factor[3] = {0, 0, 0};
+    int components[3] = {0, 1, 2};
+    CMatrixRef bodies; /* 10 x n_bodies: centre, radius, velocity, angular velocity */
+    double eta = 1.0, reg = 5e-3, epsilon_distance = 1e-5;
+};
+
+/* streamline.hpp:29, plus the tracer's status (skelly_hip.h: the larger of
+ * the two directions' codes, 0 when both reached t_final). */
+struct StreamLine {
+    MatrixXd x, val; /* 3 x n_points */
+    std::vector<double> time;
+    int status = 0;
+};
+
+/* One joined line per column of x0 (3 x n_seeds): the backward path reversed
+ * and without the seed it shares, then the forward path
+ * (join_back_and_forward, streamline.cpp:56-65). */
+inline std::vector<StreamLine> trace_streamlines(const StreamlineField &f, const CMatrixRef &x0,
+                                                 double dt_init = 0.1, double t_final = 1.0,
+                                                 double abs_err = 1e-10, double rel_err = 1e-6,
+                                                 bool back_integrate = true,
+                                                 long max_points = 4096) {
+    const long n = x0.size() / 3, n_jobs = n * (back_integrate ? 2 : 1);
+    std::vector<double> x(3 * n_jobs * max_points), val(3 * n_jobs * max_points),
+        t(n_jobs * max_points);
+    std::vector<int> count(n_jobs), status(n_jobs);
+    const double background[9] = {f.uniform[0],      f.uniform[1],      f.uniform[2],
+                                  f.scale_factor[0], f.scale_factor[1], f.scale_factor[2],
+                                  (double)f.components[0], (double)f.components[1],
+                                  (double)f.components[2]};
+    check_rc(skelly_trace_streamlines_host(
+                 f.r_sl.ptr, f.f_sl.ptr, f.r_sl.size() / 3, f.r_dl.ptr, f.f_dl.ptr,
+                 f.r_dl.size() / 3, f.r_rot.ptr, f.torques.ptr, f.r_rot.size() / 3, f.r_os.ptr,
+                 f.f_os.ptr, f.r_os.size() / 3, f.has_background ? background : nullptr,
+                 f.bodies.ptr, f.bodies.size() / 10, x0.ptr, n, back_integrate ? 1 : 0, f.eta,
+                 f.reg, f.epsilon_distance, dt_init, t_final, abs_err, rel_err, max_points,
+                 x.data(), t.data(), val.data(), count.data(), status.data()),
+             "trace_streamlines");
+    std::vector<StreamLine> lines(n);
+    for (long i = 0; i < n; ++i) {
+        const long back = back_integrate ? count[n + i] - 1 : 0; /* without the seed */
+        StreamLine &s = lines[i];
+        s.x = MatrixXd(3, back + count[i]);
+        s.val = MatrixXd(3, back + count[i]);
+        s.time.resize(back + count[i]);
+        s.status = back_integrate && status[n + i] > status[i] ? status[n + i] : status[i];
+        for (long c = 0; c < back + count[i]; ++c) {
+            /* row of the job arrays that is column c of the line */
+            const long row = c < back ? (n + i) * max_points + (back - c)
+                                      : i * max_points + (c - back);
+            for (int j = 0; j < 3; ++j) {
+                s.x(j, c) = x[3 * row + j];
+                s.val(j, c) = val[3 * row + j];
+            }
+            s.time[c] = t[row];
+        }
+    }
+    return lines;
+}
+
 /* Mirror of the reference's string-keyed backend selection
  * (fiber_container_base.cpp:20-33, periphery.cpp:337-352): "HIP" is this
  * engine; the reference's "CPU"/"FMM" backends are out of scope. */

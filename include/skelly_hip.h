@@ -251,6 +251,76 @@ int skelly_oseen_tensor_batched_device(const double *d_pts, double *d_G, long lo
                                        long long n, double eta, double reg,
                                        double epsilon_distance, void *stream);
 
+/* ---- streamlines ----
+ *
+ * Integrates dx/dt = u(x) from every seed with adaptive Cash-Karp 5(4) in one
+ * kernel launch, a workgroup per job, no host round trip per step. A job is
+ * one seed in one direction: job j < n_seeds runs seed j from t = 0 to
+ * +t_final, and with back_integrate != 0 job n_seeds + j runs it to -t_final
+ * (n_jobs = n_seeds or 2 n_seeds).
+ *
+ * u is the sum of four source sets, each possibly empty (n = 0, pointers
+ * unread): Stokeslets (sl: 3 doubles a source, skelly_stokeslet_*'s field),
+ * stresslets (dl: 9, skelly_stresslet_*), rotlets (rot: 3, skelly_rotlet_*)
+ * and regularized Stokeslets (os: 3, skelly_oseen_contract_*), scaled and
+ * regularized as those entry points do with (eta, reg, epsilon_distance);
+ * plus the background, `background` = {uniform[3], scale[3], components[3]}
+ * (9 doubles ON THE HOST in both forms, read during the call, components as
+ * 0.0/1.0/2.0; NULL for none): u_j += uniform_j + x[components_j] * scale_j.
+ * A point inside a body, |x - c_b| < radius_b, has u = U_b + w_b x (x - c_b)
+ * instead, the last such body deciding; bodies is (n_bodies, 10) rows
+ * {c[3], radius, U[3], w[3]}.
+ *
+ * Step control (Boost.Odeint controlled_runge_kutta with
+ * default_error_checker(abs_err, rel_err, 1, 1) under integrate_adaptive;
+ * DESIGN.md, "Streamlines on the device"): the first step is dt_init, the
+ * start of every step is recorded with its velocity, a step is retried with
+ * dt * max(0.9 err^(-1/3), 0.2) while err > 1, and the next one grows by
+ * 0.9 max(5^-5, err)^(-1/5) when err < 0.5; the last step is clipped to end
+ * on t_final and the end point is recorded.
+ *
+ * Outputs per job: x (max_points x 3), t (max_points), val (max_points x 3,
+ * the velocity at each recorded point), of which the first count[job] rows are
+ * written, and status[job]:
+ *   0  t_final reached;
+ *   1  |u| > 1e3 at a recorded point (a singularity; the point is the last
+ *      one recorded);
+ *   2  the buffer is full: count == max_points;
+ *   3  the step control gave up (1000 rejections of one step, a step that
+ *      does not move t, or more than 4 max_points + 1000 tries).
+ * count is written as -1 before the launch, so a job that never ran shows.
+ * Results are bit-reproducible, independent of which other seeds share the
+ * call and of the pair kernels' slice and fast-path switches.
+ *
+ * The device form is asynchronous on `stream`, performs no synchronization
+ * and packs the sources into the stream's persistent workspace; the host form
+ * takes host pointers throughout. A negative count (max_points included) is an
+ * error before any HIP call; n_seeds == 0 returns 0 and touches nothing. */
+int skelly_trace_streamlines_device(
+    const double *d_sl_r, const double *d_sl_f, long long n_sl,
+    const double *d_dl_r, const double *d_dl_f, long long n_dl,
+    const double *d_rot_r, const double *d_rot_f, long long n_rot,
+    const double *d_os_r, const double *d_os_f, long long n_os,
+    const double *background, const double *d_bodies, long long n_bodies,
+    const double *d_seeds, long long n_seeds, int back_integrate,
+    double eta, double reg, double epsilon_distance,
+    double dt_init, double t_final, double abs_err, double rel_err, long long max_points,
+    double *d_x, double *d_t, double *d_val, int *d_count, int *d_status, void *stream);
+int skelly_trace_streamlines_host(
+    const double *sl_r, const double *sl_f, long long n_sl,
+    const double *dl_r, const double *dl_f, long long n_dl,
+    const double *rot_r, const double *rot_f, long long n_rot,
+    const double *os_r, const double *os_f, long long n_os,
+    const double *background, const double *bodies, long long n_bodies,
+    const double *seeds, long long n_seeds, int back_integrate,
+    double eta, double reg, double epsilon_distance,
+    double dt_init, double t_final, double abs_err, double rel_err, long long max_points,
+    double *x, double *t, double *val, int *count, int *status);
+
+/* Threads of a tracer workgroup: a compile-time constant of the library
+ * (SKELLY_TRACE_BLOCK), for the record of a measurement. */
+int skelly_trace_block_size(void);
+
 /* ---- measurement helpers ---- */
 
 /* Measured fp64 FMA throughput (TFLOP/s) of the current device via a pure

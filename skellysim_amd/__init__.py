@@ -40,6 +40,8 @@ from .evaluator import (  # noqa: F401
     stokeslet_pressure_device,
     stresslet_pressure_device,
     oseen_contract_pressure_device,
+    trace_streamlines_device,
+    join_streamlines,
 )
 from .sharded import ShardedPairEvaluator, shard_sizes, allgather_rows  # noqa: F401
 

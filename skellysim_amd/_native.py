@@ -63,6 +63,24 @@ PRESSURE_FAMILY = {
 }
 
 
+class TraceCount(ctypes.c_longlong):
+    """The `long long` counts of the streamline entry points: a type of its
+    own for the reason PressureCount is one (tests/test_streamlines_cpu.py
+    checks these entry points' argument contract)."""
+
+
+def _trace_args(p, ip):
+    """skelly_trace_streamlines_*: p the double pointers, ip the int pointers.
+    `background` is a host pointer in both forms."""
+    t = TraceCount
+    return ([p, p, t] * 4                       # sl, dl, rot, os: r, f, n
+            + [_DP, p, t]                       # background (host), bodies, n_bodies
+            + [p, t, _I]                        # seeds, n_seeds, back_integrate
+            + [_D] * 3                          # eta, reg, epsilon_distance
+            + [_D] * 4 + [t]                    # dt_init, t_final, abs_err, rel_err, max_points
+            + [p, p, p, ip, ip])                # x, t, val, count, status
+
+
 def strength_first(symbol):
     """Whether skelly_<symbol>_* take (r_src, f_src, n_src, r_trg, ...), the
     strength orders, and not (r_src, r_trg, density, ...)."""
@@ -90,6 +108,9 @@ SIGNATURES = {
     "skelly_fp64_peak_tflops": (_I, [_DP]),
     "skelly_issue_cost_probe": (_I, [_DP]),
     "skelly_rsq_accuracy_probe": (_I, [_PV, _PV, _PV, _LL, _PV]),
+    "skelly_trace_streamlines_host": (_I, _trace_args(_DP, ctypes.POINTER(_I))),
+    "skelly_trace_streamlines_device": (_I, _trace_args(_PV, _PV) + [_PV]),
+    "skelly_trace_block_size": (_I, []),
 }
 for _name, _family in PAIR_FAMILY.items():
     SIGNATURES[f"skelly_{_name}_host"] = (_I, _PAIR_ARGS[_family](_DP))

@@ -1555,6 +1555,10 @@ hipError_t launch_rsq_probe(const double *x, double *seed, double *refined, long
 
 } // namespace skelly
 
+/* The streamline tracer: a kernel of its own over the functors, pack_sources
+ * and the workspace above. */
+#include "streamline_kernel.hpp"
+
 /* Runtime override of the persistent split-K workspace (see
  * g_persistent_ws above): hipGraph capture of the GMRES iteration
  * (gmres.py use_graph) requires it — hipMallocAsync nodes cannot be

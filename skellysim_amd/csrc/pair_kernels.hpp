@@ -44,6 +44,32 @@ hipError_t launch_pair_kernel(PairKernel kernel, const double *r_src, const doub
 long long persistent_ws_bytes(hipStream_t stream);
 void release_persistent_ws(hipStream_t stream);
 
+/* One launch of the streamline tracer (streamline_kernel.hpp), asynchronous on
+ * `stream`: the four source sets are packed into the stream's workspace and
+ * every seed is integrated forward (and backward with back_integrate) by a
+ * workgroup of its own. All pointers are device pointers. */
+struct TraceRequest {
+    /* Stokeslet, Stresslet (9 doubles a source), Rotlet, OseenContract */
+    const double *r[4], *f[4];
+    long long n[4];
+    double scale_stokes, scale_oseen; /* the prefactors of the velocity entry points */
+    double reg, eps;
+    double uniform[3], bg_scale[3]; /* background: uniform_j + x[components_j] * bg_scale_j */
+    int components[3];
+    const double *bodies; /* (n_bodies, 10): centre, radius, velocity, angular velocity */
+    long long n_bodies;
+    const double *seeds; /* (n_seeds, 3) */
+    long long n_seeds;
+    int back_integrate; /* jobs: n_seeds forward, then n_seeds backward */
+    double dt_init, t_final, abs_err, rel_err;
+    long long max_points;
+    double *x, *t, *val; /* (n_jobs, max_points, 3), (n_jobs, max_points), as x */
+    int *count, *status; /* (n_jobs) */
+};
+hipError_t launch_trace_streamlines(const TraceRequest &q, hipStream_t stream);
+/* Threads of a tracer workgroup (compile-time, SKELLY_TRACE_BLOCK). */
+int trace_block_size();
+
 /* Dense builders and the fp64 peak microbenchmark. */
 hipError_t launch_oseen_tensor_batched(const double *pts, double *G, long long nf, long long n,
                                        double eta, double reg, double eps, hipStream_t stream);

@@ -174,6 +174,58 @@ int pair_host(const char *where, PairKernel kernel, const double *r_src, const d
 double scale_stokes(double eta) { return kOneOver8Pi / eta; }          /* kernels.cu:59 */
 double scale_oseen(double eta) { return 1.0 / (8.0 * M_PI * eta); }    /* kernels.cpp:94,213 */
 
+/* The arguments of a streamline entry point as the launcher's request, after
+ * the check that comes before any HIP call. True (message recorded) when a
+ * count is negative. */
+bool trace_request(const char *where, skelly::TraceRequest &q, const double *sl_r,
+                   const double *sl_f, long long n_sl, const double *dl_r, const double *dl_f,
+                   long long n_dl, const double *rot_r, const double *rot_f, long long n_rot,
+                   const double *os_r, const double *os_f, long long n_os,
+                   const double *background, const double *bodies, long long n_bodies,
+                   const double *seeds, long long n_seeds, int back_integrate, double eta,
+                   double reg, double eps, double dt_init, double t_final, double abs_err,
+                   double rel_err, long long max_points, double *x, double *t, double *val,
+                   int *count, int *status) {
+    if (negative_size(where, n_sl, n_dl) || negative_size(where, n_rot, n_os) ||
+        negative_size(where, n_bodies, n_seeds) || negative_size(where, max_points))
+        return true;
+    q = skelly::TraceRequest{};
+    const double *r[4] = {sl_r, dl_r, rot_r, os_r}, *f[4] = {sl_f, dl_f, rot_f, os_f};
+    const long long n[4] = {n_sl, n_dl, n_rot, n_os};
+    for (int k = 0; k < 4; ++k) {
+        q.r[k] = r[k];
+        q.f[k] = f[k];
+        q.n[k] = n[k];
+    }
+    q.scale_stokes = scale_stokes(eta);
+    q.scale_oseen = scale_oseen(eta);
+    q.reg = reg;
+    q.eps = eps;
+    if (n_seeds == 0)
+        background = nullptr; /* nothing is read for a call that does nothing */
+    for (int j = 0; j < 3; ++j) {
+        q.uniform[j] = background ? background[j] : 0.0;
+        q.bg_scale[j] = background ? background[3 + j] : 0.0;
+        q.components[j] = background ? (int)background[6 + j] : j;
+    }
+    q.bodies = bodies;
+    q.n_bodies = n_bodies;
+    q.seeds = seeds;
+    q.n_seeds = n_seeds;
+    q.back_integrate = back_integrate;
+    q.dt_init = dt_init;
+    q.t_final = t_final;
+    q.abs_err = abs_err;
+    q.rel_err = rel_err;
+    q.max_points = max_points;
+    q.x = x;
+    q.t = t;
+    q.val = val;
+    q.count = count;
+    q.status = status;
+    return false;
+}
+
 } // namespace
 
 extern "C" {
@@ -444,6 +496,103 @@ int skelly_oseen_tensor_batched_device(const double *d_pts, double *d_G, long lo
                                             (hipStream_t)stream));
     return 0;
 }
+
+/* ---- streamlines ---- */
+
+int skelly_trace_streamlines_device(
+    const double *d_sl_r, const double *d_sl_f, long long n_sl, const double *d_dl_r,
+    const double *d_dl_f, long long n_dl, const double *d_rot_r, const double *d_rot_f,
+    long long n_rot, const double *d_os_r, const double *d_os_f, long long n_os,
+    const double *background, const double *d_bodies, long long n_bodies, const double *d_seeds,
+    long long n_seeds, int back_integrate, double eta, double reg, double epsilon_distance,
+    double dt_init, double t_final, double abs_err, double rel_err, long long max_points,
+    double *d_x, double *d_t, double *d_val, int *d_count, int *d_status, void *stream) {
+    const char *where = "skelly_trace_streamlines_device";
+    skelly::TraceRequest q;
+    if (trace_request(where, q, d_sl_r, d_sl_f, n_sl, d_dl_r, d_dl_f, n_dl, d_rot_r, d_rot_f,
+                      n_rot, d_os_r, d_os_f, n_os, background, d_bodies, n_bodies, d_seeds,
+                      n_seeds, back_integrate, eta, reg, epsilon_distance, dt_init, t_final,
+                      abs_err, rel_err, max_points, d_x, d_t, d_val, d_count, d_status))
+        return -1;
+    if (n_seeds == 0)
+        return 0;
+    CHK(where, skelly::launch_trace_streamlines(q, (hipStream_t)stream));
+    return 0;
+}
+
+int skelly_trace_streamlines_host(
+    const double *sl_r, const double *sl_f, long long n_sl, const double *dl_r,
+    const double *dl_f, long long n_dl, const double *rot_r, const double *rot_f,
+    long long n_rot, const double *os_r, const double *os_f, long long n_os,
+    const double *background, const double *bodies, long long n_bodies, const double *seeds,
+    long long n_seeds, int back_integrate, double eta, double reg, double epsilon_distance,
+    double dt_init, double t_final, double abs_err, double rel_err, long long max_points,
+    double *x, double *t, double *val, int *count, int *status) {
+    const char *where = "skelly_trace_streamlines_host";
+    skelly::TraceRequest q;
+    if (trace_request(where, q, sl_r, sl_f, n_sl, dl_r, dl_f, n_dl, rot_r, rot_f, n_rot, os_r,
+                      os_f, n_os, background, bodies, n_bodies, seeds, n_seeds, back_integrate,
+                      eta, reg, epsilon_distance, dt_init, t_final, abs_err, rel_err, max_points,
+                      x, t, val, count, status))
+        return -1;
+    if (n_seeds == 0)
+        return 0;
+    const size_t n_jobs = (size_t)n_seeds * (back_integrate ? 2 : 1);
+    const size_t rows = n_jobs * (size_t)max_points;
+    /* one block for the call: the inputs, then x, val, t, count, status */
+    const int width[4] = {3, 9, 3, 3};
+    size_t in_doubles = (size_t)n_bodies * 10 + (size_t)n_seeds * 3;
+    for (int k = 0; k < 4; ++k)
+        in_doubles += (size_t)q.n[k] * (3 + width[k]);
+    const size_t bytes = (in_doubles + rows * 7) * 8 + n_jobs * 2 * sizeof(int);
+
+    Context &c = ctx();
+    std::lock_guard<std::mutex> lock(c.mu);
+    CHK(where, c.ensure_stream());
+    double *block = nullptr;
+    CHK(where, hipMalloc((void **)&block, bytes));
+    /* everything below frees the block on its way out */
+    hipError_t err = hipSuccess;
+    double *at = block;
+    auto upload = [&](const double *&p, size_t doubles) {
+        if (doubles && err == hipSuccess)
+            err = hipMemcpyAsync(at, p, doubles * 8, hipMemcpyHostToDevice, c.stream);
+        p = at;
+        at += doubles;
+    };
+    for (int k = 0; k < 4; ++k) {
+        upload(q.r[k], (size_t)q.n[k] * 3);
+        upload(q.f[k], (size_t)q.n[k] * width[k]);
+    }
+    upload(q.bodies, (size_t)n_bodies * 10);
+    upload(q.seeds, (size_t)n_seeds * 3);
+    q.x = at;
+    q.val = q.x + rows * 3;
+    q.t = q.val + rows * 3;
+    q.count = reinterpret_cast<int *>(q.t + rows);
+    q.status = q.count + n_jobs;
+    if (err == hipSuccess)
+        err = skelly::launch_trace_streamlines(q, c.stream);
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(x, q.x, rows * 3 * 8, hipMemcpyDeviceToHost, c.stream);
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(val, q.val, rows * 3 * 8, hipMemcpyDeviceToHost, c.stream);
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(t, q.t, rows * 8, hipMemcpyDeviceToHost, c.stream);
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(count, q.count, n_jobs * sizeof(int), hipMemcpyDeviceToHost,
+                             c.stream);
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(status, q.status, n_jobs * sizeof(int), hipMemcpyDeviceToHost,
+                             c.stream);
+    const hipError_t sync = hipStreamSynchronize(c.stream);
+    (void)hipFree(block);
+    CHK(where, err);
+    CHK(where, sync);
+    return 0;
+}
+
+int skelly_trace_block_size(void) { return skelly::trace_block_size(); }
 
 int skelly_fp64_peak_tflops(double *out_tflops) {
     Context &c = ctx();

@@ -395,3 +395,111 @@ def oseen_contract_pressure_device(r_src, r_trg, density, reg=5e-3, epsilon_dist
                                    out=None):
     """Pressure of oseen_contract_device's field."""
     return _device_pair(_OSEEN_PRESSURE, r_src, density, r_trg, out, (reg, epsilon_distance))
+
+
+# ---------------------------------------------------------------------------
+# streamlines on device tensors: one launch, a workgroup per seed and direction
+# ---------------------------------------------------------------------------
+
+# the four source sets of the tracer, in the library's order: (name, doubles
+# per source of the strength, label of the strength in error messages)
+TRACE_SETS = (("stokeslet", 3, "forces"), ("stresslet", 9, "f_dl"),
+              ("rotlet", 3, "torques"), ("oseen", 3, "forces"))
+# status codes of a traced job (include/skelly_hip.h)
+TRACE_DONE, TRACE_SINGULAR, TRACE_FULL, TRACE_GAVE_UP = 0, 1, 2, 3
+
+
+def _background9(background):
+    """(uniform, scale_factor, components) -> the 9 host doubles the library
+    reads, or None."""
+    if background is None:
+        return None
+    uniform, scale, components = background
+    comp = np.asarray(components, dtype=np.int64).reshape(3)
+    if ((comp < 0) | (comp > 2)).any():
+        raise ValueError(f"background components: expected 0, 1 or 2, got {comp.tolist()}")
+    return np.concatenate([np.asarray(uniform, np.float64).reshape(3),
+                           np.asarray(scale, np.float64).reshape(3), comp.astype(np.float64)])
+
+
+def trace_streamlines_device(seeds, eta, stokeslet=None, stresslet=None, rotlet=None, oseen=None,
+                             background=None, bodies=None, dt_init=0.1, t_final=1.0,
+                             abs_err=1e-10, rel_err=1e-6, back_integrate=True, max_points=4096,
+                             reg=5e-3, epsilon_distance=1e-5):
+    """Streamlines of the summed field from every row of `seeds` (n, 3), in
+    one kernel launch on torch's current stream (asynchronous, no
+    synchronization; skelly_trace_streamlines_device, include/skelly_hip.h).
+
+    stokeslet / stresslet / rotlet / oseen: (r_src (m, 3), strength (m, 3 or
+    9)) device tensors or None, the fields of stokeslet_device,
+    stresslet_device, rotlet_device and oseen_contract_device. background:
+    (uniform, scale_factor, components) host values, u_j += uniform_j +
+    x[components_j] * scale_factor_j. bodies: (n_b, 10) device tensor of rows
+    {centre, radius, velocity, angular velocity}; a point inside one moves
+    rigidly with it.
+
+    Returns a dict of device tensors per job (job j < n runs seed j forward,
+    job n + j backward when back_integrate): x (n_jobs, max_points, 3),
+    t (n_jobs, max_points), val as x (the velocity at the points), count and
+    status (n_jobs,) int32. Rows past count[job] are not written."""
+    import torch
+    seeds = _dev_rows(seeds, 3, "seeds")
+    args = []
+    for (name, dim, label), pair in zip(TRACE_SETS, (stokeslet, stresslet, rotlet, oseen)):
+        if pair is None:
+            args += [None, None, 0]
+            continue
+        r = _dev_rows(pair[0], 3, f"{name} r_src")
+        f = _dev_rows(pair[1], dim, f"{name} {label}")
+        _same_length(f.shape[0], f"{name} {label}", r.shape[0], f"{name} r_src")
+        args += [r, f, r.shape[0]]
+    if bodies is not None:
+        bodies = _dev_rows(bodies, 10, "bodies")
+    bg = _background9(background)
+    max_points = int(max_points)
+    if max_points < 1:
+        raise ValueError(f"max_points: expected at least 1, got {max_points}")
+    n = seeds.shape[0]
+    n_jobs = n * (2 if back_integrate else 1)
+    out = {
+        "x": torch.empty((n_jobs, max_points, 3), dtype=torch.float64, device=seeds.device),
+        "t": torch.empty((n_jobs, max_points), dtype=torch.float64, device=seeds.device),
+        "val": torch.empty((n_jobs, max_points, 3), dtype=torch.float64, device=seeds.device),
+        "count": torch.empty((n_jobs,), dtype=torch.int32, device=seeds.device),
+        "status": torch.empty((n_jobs,), dtype=torch.int32, device=seeds.device),
+    }
+    ptr = lambda t: None if t is None else _dptr(t)
+    rc = _native.lib().skelly_trace_streamlines_device(
+        *[a if isinstance(a, int) else ptr(a) for a in args],
+        None if bg is None else _ptr(bg), ptr(bodies), 0 if bodies is None else bodies.shape[0],
+        _dptr(seeds), n, int(bool(back_integrate)),
+        float(eta), float(reg), float(epsilon_distance),
+        float(dt_init), float(t_final), float(abs_err), float(rel_err), max_points,
+        *[_dptr(out[k]) for k in ("x", "t", "val", "count", "status")], _stream_ptr())
+    _native.check(rc, "trace_streamlines_device")
+    return out
+
+
+def join_streamlines(x, t, val, count, status, n_seeds):
+    """The per-job arrays of a trace (host arrays, jobs as the library orders
+    them) as one line per seed, joined as the reference's
+    join_back_and_forward does (streamline.cpp:56-65): the backward path
+    reversed and without the seed it shares with the forward path, then the
+    forward path. Returns a list of dicts {x (m, 3), val (m, 3), time (m,),
+    status}, status being the larger of the two jobs' codes (0 only when both
+    directions reached t_final)."""
+    x, t, val = np.asarray(x), np.asarray(t), np.asarray(val)
+    count, status = np.asarray(count), np.asarray(status)
+    back = len(count) == 2 * n_seeds
+    lines = []
+    for i in range(n_seeds):
+        c = int(count[i])
+        px, pt, pv, st = x[i, :c], t[i, :c], val[i, :c], int(status[i])
+        if back:
+            j, cb = n_seeds + i, int(count[n_seeds + i])
+            px = np.concatenate([x[j, 1:cb][::-1], px])
+            pt = np.concatenate([t[j, 1:cb][::-1], pt])
+            pv = np.concatenate([val[j, 1:cb][::-1], pv])
+            st = max(st, int(status[j]))
+        lines.append({"x": px, "val": pv, "time": pt, "status": st})
+    return lines

@@ -335,6 +335,102 @@ def surface_force_torque(points, normals, weights, stress, origin):
     return wt.sum(axis=0), np.cross(arm, wt).sum(axis=0)
 
 
+# ---------------------------------------------------------------------------
+# Streamlines: dx/dt = u(x) with u the field of velocity_at_targets (plus
+# point/background sources and the rigid motion inside bodies, as the
+# listener's velocity_field has them), integrated on the device by one
+# persistent kernel launch for all seeds (evaluator.trace_streamlines_device).
+# ---------------------------------------------------------------------------
+
+def streamline_source_sets(eta, fiber=None, shell=None, bodies=None, sources=None, to=None):
+    """The tracer's inputs from velocity_at_targets' terms: dict(stokeslet,
+    stresslet, rotlet, oseen = (r_src, strength) or None, background, bodies).
+
+    fiber, shell, bodies: the dicts of velocity_at_targets (fiber self terms
+    are never subtracted: the post-processing form). bodies may also carry
+    radii (n_b,), velocities (n_b, 3) and angular_velocities (n_b, 3): points
+    inside a body then move rigidly with it (system.cpp:363-371).
+    sources: dict with any of force_pos/forces (point forces, the regularized
+    Stokeslet), torque_pos/torques (point torques) and background =
+    (uniform, scale_factor, components).
+    `to` maps each array (numpy or tensor) to the tensor to concatenate."""
+    to = to or (lambda a: a)
+    sl, dl, rot, os_ = [], [], [], []
+    if fiber is not None and fiber["r_src"].shape[0]:
+        sl.append((to(fiber["r_src"]), to(fiber["forces"]) * to(fiber["weights"])[:, None]))
+    if shell is not None and shell["node_pos"].shape[0]:
+        dl.append((to(shell["node_pos"]),
+                   double_layer_strength(to(shell["node_normal"]), to(shell["density"]), eta)))
+    rigid = None
+    if bodies is not None:
+        if bodies["node_pos"].shape[0]:
+            dl.append((to(bodies["node_pos"]),
+                       double_layer_strength(to(bodies["node_normals"]),
+                                             to(bodies["densities"]), eta)))
+        if bodies["centers"].shape[0]:
+            sl.append((to(bodies["centers"]), to(bodies["forces"])))
+            rot.append((to(bodies["centers"]), to(bodies["torques"])))
+            if bodies.get("radii") is not None:
+                rigid = torch.cat([to(bodies["centers"]), to(bodies["radii"]).reshape(-1, 1),
+                                   to(bodies["velocities"]), to(bodies["angular_velocities"])],
+                                  dim=1).contiguous()
+    background = None
+    if sources is not None:
+        if sources.get("forces") is not None and len(sources["forces"]):
+            os_.append((to(sources["force_pos"]), to(sources["forces"])))
+        if sources.get("torques") is not None and len(sources["torques"]):
+            rot.append((to(sources["torque_pos"]), to(sources["torques"])))
+        background = sources.get("background")
+
+    def cat(parts):
+        if not parts:
+            return None
+        return (torch.cat([p[0] for p in parts]).contiguous(),
+                torch.cat([p[1] for p in parts]).contiguous())
+
+    return dict(stokeslet=cat(sl), stresslet=cat(dl), rotlet=cat(rot), oseen=cat(os_),
+                background=background, bodies=rigid)
+
+
+def streamlines_at_seeds(x0, eta, fiber=None, shell=None, bodies=None, sources=None,
+                         dt_init=0.1, t_final=1.0, abs_err=1e-10, rel_err=1e-6,
+                         back_integrate=True, max_points=4096, backend=None):
+    """Streamlines of velocity_at_targets' field through every row of x0
+    (n, 3), as StreamLine::compute (streamline.cpp:67-113) integrates them:
+    adaptive Cash-Karp 5(4) from t = 0 to t_final, and to -t_final when
+    back_integrate, stopping where |u| > 1e3. All seeds are traced in one
+    kernel launch with the sources uploaded and packed once; the terms
+    (numpy arrays or tensors) are those of streamline_source_sets.
+
+    Returns one dict per seed, {x (m, 3), val (m, 3), time (m,), status} as
+    numpy arrays (this call waits for the kernel): the joined line of
+    evaluator.join_streamlines, val the velocity at its points, status 0 when
+    t_final was reached both ways (else the tracer's code: 1 singularity,
+    2 max_points recorded, 3 step control gave up). backend: a HipBackend
+    (default: one on x0's device, cuda:0 for numpy)."""
+    import numpy as np
+    from .evaluator import join_streamlines
+    if backend is None:
+        from .system_fd import HipBackend
+        backend = HipBackend(x0.device) if torch.is_tensor(x0) else HipBackend()
+
+    def to(a):
+        if not torch.is_tensor(a):
+            a = np.ascontiguousarray(a, dtype=np.float64)
+        return backend._t(a)
+
+    seeds = to(x0).reshape(-1, 3)
+    n = seeds.shape[0]
+    if n == 0:
+        return []
+    sets = streamline_source_sets(eta, fiber, shell, bodies, sources, to)
+    out = backend.trace_streamlines(
+        seeds, eta, **sets, dt_init=dt_init, t_final=t_final, abs_err=abs_err, rel_err=rel_err,
+        back_integrate=back_integrate, max_points=max_points)
+    host = {k: v.cpu().numpy() for k, v in out.items()}
+    return join_streamlines(host["x"], host["t"], host["val"], host["count"], host["status"], n)
+
+
 class ShellOperator:
     """HBM-resident periphery dense operators (M_inv, stresslet+complementary).
 

@@ -32,7 +32,13 @@ evaluation per point instead of six velocity probes), a
 block (column t = row-major du_i/dx_j at target t) to the response, a
 `"pressure": {"x": ...}` entry a 1 x n `pressure` block (pressure_field) and
 a `"stress": {"x": ...}` entry a 9 x n `stress` block (stress_field, column
-t = row-major sigma_ij at target t)."""
+t = row-major sigma_ij at target t). `"device": true` in the `streamlines`
+map traces all its seeds on the device in one kernel launch
+(flows.streamlines_at_seeds: the frame's sources built, uploaded and packed
+once, the reference's Cash-Karp 5(4) step control instead of scipy's RK45);
+each line then also carries the tracer's `status`, and `"max_points"` in the
+same map sizes its buffers (default 4096 points a direction). Vortex lines
+ignore the key."""
 
 import argparse
 import os
@@ -397,6 +403,65 @@ def integrate_streamline(field_fn, x0, dt_init=0.1, t_final=1.0, abs_err=1e-10,
     return {"x": x, "val": val, "time": t.tolist()}
 
 
+def streamline_terms(frame, eta, shell_geometry=None, body_geometry=None, sources=None):
+    """velocity_field's sources as the terms of flows.streamlines_at_seeds
+    (fiber, shell, bodies, sources), built once from the frame with the same
+    helpers."""
+    terms = dict(fiber=None, shell=None, bodies=None, sources=None)
+    if sources is not None:
+        psc, bs = sources
+        src = {}
+        if psc is not None:
+            time = float(frame.get("time", 0.0))
+            live = [p for p in psc.points if not (p.time_to_live and time >= p.time_to_live)]
+            forcers = [p for p in live if p.force.any()]
+            torquers = [p for p in live if p.torque.any()]
+            if forcers:
+                src["force_pos"] = np.stack([p.position for p in forcers])
+                src["forces"] = np.stack([p.force for p in forcers])
+            if torquers:
+                src["torque_pos"] = np.stack([p.position for p in torquers])
+                src["torques"] = np.stack([p.torque for p in torquers])
+        if bs is not None and bs.is_active():
+            src["background"] = (bs.uniform, bs.scale_factor, bs.components)
+        terms["sources"] = src
+    fibers = fibers_from_frame(frame, eta)
+    if fibers:
+        r_src, wf = _fiber_sources(fibers)
+        terms["fiber"] = dict(r_src=r_src, forces=wf, weights=np.ones(len(wf)))
+    dens = _shell_density(frame, shell_geometry)
+    if dens is not None:
+        terms["shell"] = dict(node_pos=np.asarray(shell_geometry["nodes"], float),
+                              node_normal=np.asarray(shell_geometry["normals"], float),
+                              density=dens)
+    bodies = bodies_from_frame(frame, body_geometry) \
+        if body_geometry is not None else []
+    if bodies:
+        nodes, normals, dens, centers, ft = _body_sources(fibers, bodies)
+        terms["bodies"] = dict(
+            node_pos=nodes, node_normals=normals, densities=dens, centers=centers,
+            forces=ft[:, 0:3], torques=ft[:, 3:6],
+            radii=np.array([b.radius for b in bodies], float),
+            velocities=np.stack([b.velocity for b in bodies]),
+            angular_velocities=np.stack([b.angular_velocity for b in bodies]))
+    return terms
+
+
+def _device_streamlines(frame, req, x0, eta, compute, shell_geometry, body_geometry, sources):
+    """The `"device": true` route of a streamlines request: the frame's
+    sources built once, all seeds traced by flows.streamlines_at_seeds.
+    Each line also carries the tracer's `status`."""
+    from .flows import streamlines_at_seeds
+    lines = streamlines_at_seeds(
+        x0, eta, **streamline_terms(frame, eta, shell_geometry, body_geometry, sources),
+        dt_init=float(req.get("dt_init", 0.1)), t_final=float(req.get("t_final", 1.0)),
+        abs_err=float(req.get("abs_err", 1e-10)), rel_err=float(req.get("rel_err", 1e-6)),
+        back_integrate=bool(req.get("back_integrate", True)),
+        max_points=int(req.get("max_points", 4096)), backend=compute)
+    return [{"x": eigen_encode_3xn(s["x"]), "val": eigen_encode_3xn(s["val"]),
+             "time": s["time"].tolist(), "status": s["status"]} for s in lines]
+
+
 def process_streamlines(frame, req, eta, compute, shell_geometry,
                         vortex=False, body_geometry=None, sources=None):
     """process_streamlines / process_vortexlines (listener.cpp:51-74): one
@@ -409,6 +474,9 @@ def process_streamlines(frame, req, eta, compute, shell_geometry,
     x0 = np.asarray(x0, float).reshape(-1, 3) if np.size(x0) else np.zeros((0, 3))
     if not len(x0):
         return []
+    if req.get("device") and not vortex:
+        return _device_streamlines(frame, req, x0, eta, compute, shell_geometry,
+                                   body_geometry, sources)
     field = lambda pts: velocity_field(frame, pts, eta, compute,
                                        shell_geometry, body_geometry,
                                        sources)

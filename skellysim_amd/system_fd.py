@@ -121,6 +121,25 @@ class HipBackend:
     def oseen_contract_pressure(self, r_src, r_trg, density):
         return self._eval("oseen_contract_pressure", (r_src, r_trg, density))
 
+    def trace_streamlines(self, seeds, eta, stokeslet=None, stresslet=None, rotlet=None,
+                          oseen=None, background=None, bodies=None, **control):
+        """evaluator.trace_streamlines_device on this device: the source sets
+        are (r_src, strength) pairs of numpy arrays or tensors (None or zero
+        rows: an empty set), `control` its step-control keywords. Returns its
+        dict of per-job arrays, tensors (asynchronous) when `seeds` is one,
+        else numpy."""
+        import torch
+        from . import evaluator
+        sets = [None if p is None or len(p[0]) == 0 else (self._t(p[0]), self._t(p[1]))
+                for p in (stokeslet, stresslet, rotlet, oseen)]
+        if bodies is not None:
+            bodies = self._t(bodies) if len(bodies) else None
+        out = evaluator.trace_streamlines_device(
+            self._t(seeds), eta, *sets, background=background, bodies=bodies, **control)
+        if torch.is_tensor(seeds):
+            return out
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
     def stresslet_times_normal(self, nodes, normals, eta):
         """Dense (3n, 3n) operator (kernels.cpp:264-287; eta-independent
         factor) — the M block of the body preconditioner."""
