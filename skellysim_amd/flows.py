@@ -33,8 +33,7 @@ product path; no CPU fallback).
 
 import torch
 
-from .evaluator import (stokeslet_device, stresslet_device, stokeslet_grad_device,
-                        stresslet_grad_device)
+from .flow_sources import default_backend as _default_backend, evaluate, flow_sources
 from .sharded import allgather_rows
 
 
@@ -45,22 +44,84 @@ def double_layer_strength(normals, density, eta):
             ).reshape(-1, 9).contiguous()
 
 
+# ---------------------------------------------------------------------------
+# Every field below is flow_sources.evaluate over the FlowSources of its
+# arguments: which sources make up a flow, in which order they are summed and
+# which backend method gives which quantity is stated there, once. The pair
+# kernels are reached through a system_fd backend's methods: `backend=None`
+# is HipBackend on r_trg's device (tensors in, tensors out, no
+# synchronization); any object with the same methods on numpy arrays serves
+# numpy inputs (the tests' closed forms). The pressure p is the Stokes
+# pressure of the same fields (prefactor 1/(4 pi), no eta dependence of its
+# own; a rotlet's is zero), the stress sigma = -p I + eta (G + G^T).
+# ---------------------------------------------------------------------------
+
+def _field(quantity, r_trg, eta, backend=None, **parts):
+    return evaluate(flow_sources(**parts), quantity, r_trg, eta, backend)
+
+
+def _shell(node_pos, node_normal, density):
+    return dict(node_pos=node_pos, node_normal=node_normal, density=density)
+
+
+def _fiber(r_src, fib_forces, weights):
+    return dict(r_src=r_src, forces=fib_forces, weights=weights)
+
+
+def _bodies(node_pos, node_normals, densities, centers, forces, torques):
+    return dict(node_pos=node_pos, node_normals=node_normals, densities=densities,
+                centers=centers, forces=forces, torques=torques)
+
+
 def periphery_flow(node_pos, node_normal, density, r_trg, eta):
-    """Velocity at r_trg due to the shell's double-layer density.
+    """Velocity at r_trg due to the shell's double-layer density
+    (Periphery::flow, periphery.cpp:55-79).
 
     node_pos, node_normal, density: (n_nodes, 3); r_trg: (n_trg, 3).
     f_dl(node)[i*3+j] = 2*eta*normal_i*density_j (periphery.cpp:68-71);
     the stresslet evaluator divides by eta (periphery.cpp:74).
     """
-    if node_pos.shape[0] == 0:
-        return torch.zeros_like(r_trg)
-    f_dl = double_layer_strength(node_normal, density, eta)
-    return stresslet_device(node_pos, f_dl, r_trg, eta)
+    return _field("velocity", r_trg, eta, shell=_shell(node_pos, node_normal, density))
+
+
+def periphery_flow_grad(node_pos, node_normal, density, r_trg, eta):
+    """Velocity gradient (n_trg, 3, 3), G[t, i, j] = du_i/dx_j, of
+    periphery_flow's field."""
+    return _field("gradient", r_trg, eta, shell=_shell(node_pos, node_normal, density))
+
+
+def periphery_flow_pressure(node_pos, node_normal, density, r_trg, eta, backend=None):
+    """Pressure (n_trg,) of periphery_flow's field."""
+    return _field("pressure", r_trg, eta, backend, shell=_shell(node_pos, node_normal, density))
+
+
+def _subtract_fiber_self(vel, wf, fiber_sizes, self_stokeslets):
+    """vel[fiber nodes] -= stokeslet_fib @ wf per fiber
+    (fiber_container_finite_difference.cpp:203-210), in place."""
+    if fiber_sizes is None:
+        raise ValueError("fiber_sizes required with self_stokeslets")
+    if all(n == fiber_sizes[0] for n in fiber_sizes):
+        # uniform fibers: one batched GEMV (rocBLAS batched under torch.bmm)
+        n = fiber_sizes[0]
+        nf = len(fiber_sizes)
+        S = self_stokeslets if torch.is_tensor(self_stokeslets) \
+            else torch.stack(list(self_stokeslets))
+        wf_flat = wf.reshape(nf, 3 * n, 1)
+        corr = torch.bmm(S, wf_flat).reshape(nf * n, 3)
+        vel[: nf * n] -= corr
+    else:
+        off = 0
+        for S, n in zip(self_stokeslets, fiber_sizes):
+            wf_flat = wf[off: off + n].reshape(-1)
+            vel[off: off + n] -= (S @ wf_flat).reshape(n, 3)
+            off += n
+    return vel
 
 
 def fiber_flow(r_src, fib_forces, weights, r_trg, eta, fiber_sizes=None,
                self_stokeslets=None):
-    """Velocity at r_trg due to fiber forces.
+    """Velocity at r_trg due to fiber forces
+    (FiberContainerFiniteDifference::flow).
 
     r_src, fib_forces: (n_fib_nodes, 3); weights: (n_fib_nodes,) — the
     per-node quadrature weights 0.5 * length * weights_0
@@ -71,29 +132,34 @@ def fiber_flow(r_src, fib_forces, weights, r_trg, eta, fiber_sizes=None,
     requires r_trg to start with the fiber nodes in order, as in the
     reference's matvec (system.cpp:298-299).
     """
-    if r_src.shape[0] == 0:
-        return torch.zeros_like(r_trg)
-    wf = fib_forces * weights[:, None]
-    vel = stokeslet_device(r_src, wf.contiguous(), r_trg, eta)
-    if self_stokeslets is not None:
-        if fiber_sizes is None:
-            raise ValueError("fiber_sizes required with self_stokeslets")
-        if all(n == fiber_sizes[0] for n in fiber_sizes):
-            # uniform fibers: one batched GEMV (rocBLAS batched under torch.bmm)
-            n = fiber_sizes[0]
-            nf = len(fiber_sizes)
-            S = self_stokeslets if torch.is_tensor(self_stokeslets) \
-                else torch.stack(list(self_stokeslets))
-            wf_flat = wf.reshape(nf, 3 * n, 1)
-            corr = torch.bmm(S, wf_flat).reshape(nf * n, 3)
-            vel[: nf * n] -= corr
-        else:
-            off = 0
-            for S, n in zip(self_stokeslets, fiber_sizes):
-                wf_flat = wf[off: off + n].reshape(-1)
-                vel[off: off + n] -= (S @ wf_flat).reshape(n, 3)
-                off += n
+    vel = _field("velocity", r_trg, eta, fiber=_fiber(r_src, fib_forces, weights))
+    if self_stokeslets is not None and r_src.shape[0]:
+        _subtract_fiber_self(vel, fib_forces * weights[:, None], fiber_sizes, self_stokeslets)
     return vel
+
+
+def fiber_flow_grad(r_src, fib_forces, weights, r_trg, eta):
+    """Velocity gradient of fiber_flow's field without the self term (the
+    reference's subtract_self = false, the post-processing form)."""
+    return _field("gradient", r_trg, eta, fiber=_fiber(r_src, fib_forces, weights))
+
+
+def fiber_flow_pressure(r_src, fib_forces, weights, r_trg, backend=None):
+    """Pressure of fiber_flow's field without the self term (as
+    fiber_flow_grad)."""
+    return _field("pressure", r_trg, None, backend, fiber=_fiber(r_src, fib_forces, weights))
+
+
+def _body_backend(r_trg, reg, epsilon_distance):
+    """HipBackend on r_trg's device; its rotlets take the caller's
+    regularization where that is not the library's default."""
+    backend = _default_backend(r_trg)
+    if (reg, epsilon_distance) != (5e-3, 1e-5):
+        def rotlet(name):
+            return lambda centers, torques, trg, eta: backend._eval(
+                name, (centers, trg, torques), eta, reg=reg, epsilon_distance=epsilon_distance)
+        backend.rotlet, backend.rotlet_grad = rotlet("rotlet"), rotlet("rotlet_grad")
+    return backend
 
 
 def body_flow(node_pos, node_normals, densities, centers, forces, torques, r_trg, eta,
@@ -103,87 +169,50 @@ def body_flow(node_pos, node_normals, densities, centers, forces, torques, r_trg
     body quadrature nodes with f_dl = 2*eta*n_i*d_j (lines 299-302), plus a
     stokeslet from the body centers with the link forces (line 327), plus a
     rotlet from the centers with the torques (line 335; always direct)."""
-    v = periphery_flow(node_pos, node_normals, densities, r_trg, eta)
-    if centers.shape[0]:
-        v = v + stokeslet_device(centers, forces, r_trg, eta)
-        from .evaluator import rotlet_device
-        v = v + rotlet_device(centers, r_trg, torques, eta, reg, epsilon_distance)
-    return v
-
-
-def velocity_at_targets(r_trg, eta, fiber=None, shell=None, bodies=None):
-    """Composite free-space velocity at arbitrary targets — the kernel
-    portion of System::velocity_at_targets (src/core/system.cpp:330-384,
-    lines 355-359: fiber flow + body flow + shell flow summed; the reference
-    additionally overwrites points inside bodies with rigid-body velocity,
-    which is host-side post-processing outside this engine).
-
-    fiber  = dict(r_src, forces, weights[, fiber_sizes, self_stokeslets])
-    shell  = dict(node_pos, node_normal, density)
-    bodies = dict(node_pos, node_normals, densities, centers, forces, torques)
-    """
-    u = torch.zeros_like(r_trg)
-    if fiber is not None:
-        u = u + fiber_flow(fiber["r_src"], fiber["forces"], fiber["weights"], r_trg, eta,
-                           fiber_sizes=fiber.get("fiber_sizes"),
-                           self_stokeslets=fiber.get("self_stokeslets"))
-    if shell is not None:
-        u = u + periphery_flow(shell["node_pos"], shell["node_normal"], shell["density"],
-                               r_trg, eta)
-    if bodies is not None:
-        u = u + body_flow(bodies["node_pos"], bodies["node_normals"], bodies["densities"],
-                          bodies["centers"], bodies["forces"], bodies["torques"], r_trg, eta)
-    return u
-
-
-def _zero_grad(r_trg):
-    return torch.zeros((r_trg.shape[0], 3, 3), dtype=r_trg.dtype, device=r_trg.device)
-
-
-def periphery_flow_grad(node_pos, node_normal, density, r_trg, eta):
-    """Velocity gradient (n_trg, 3, 3), G[t, i, j] = du_i/dx_j, of
-    periphery_flow's field: the same f_dl through the stresslet gradient
-    kernel."""
-    if node_pos.shape[0] == 0:
-        return _zero_grad(r_trg)
-    f_dl = double_layer_strength(node_normal, density, eta)
-    return stresslet_grad_device(node_pos, f_dl, r_trg, eta)
-
-
-def fiber_flow_grad(r_src, fib_forces, weights, r_trg, eta):
-    """Velocity gradient of fiber_flow's field without the self term (the
-    reference's subtract_self = false, the post-processing form)."""
-    if r_src.shape[0] == 0:
-        return _zero_grad(r_trg)
-    wf = fib_forces * weights[:, None]
-    return stokeslet_grad_device(r_src, wf.contiguous(), r_trg, eta)
+    return _field("velocity", r_trg, eta, _body_backend(r_trg, reg, epsilon_distance),
+                  bodies=_bodies(node_pos, node_normals, densities, centers, forces, torques))
 
 
 def body_flow_grad(node_pos, node_normals, densities, centers, forces, torques, r_trg, eta,
                    reg=5e-3, epsilon_distance=1e-5):
     """Velocity gradient of body_flow's field, term by term."""
-    g = periphery_flow_grad(node_pos, node_normals, densities, r_trg, eta)
-    if centers.shape[0]:
-        g = g + stokeslet_grad_device(centers, forces, r_trg, eta)
-        from .evaluator import rotlet_grad_device
-        g = g + rotlet_grad_device(centers, r_trg, torques, eta, reg, epsilon_distance)
-    return g
+    return _field("gradient", r_trg, eta, _body_backend(r_trg, reg, epsilon_distance),
+                  bodies=_bodies(node_pos, node_normals, densities, centers, forces, torques))
+
+
+def body_flow_pressure(node_pos, node_normals, densities, centers, forces, torques, r_trg, eta,
+                       backend=None):
+    """Pressure of body_flow's field, term by term; the rotlet of the
+    torques has none."""
+    return _field("pressure", r_trg, eta, backend,
+                  bodies=_bodies(node_pos, node_normals, densities, centers, forces, torques))
+
+
+def velocity_at_targets(r_trg, eta, fiber=None, shell=None, bodies=None):
+    """Composite free-space velocity at arbitrary targets — the kernel
+    portion of System::velocity_at_targets (src/core/system.cpp:330-384,
+    lines 355-359: fiber flow + shell flow + body flow, summed in
+    flow_sources.TERM_ORDER).
+
+    fiber  = dict(r_src, forces, weights[, fiber_sizes, self_stokeslets]):
+             with self_stokeslets, fiber_flow's self term is subtracted from
+             the sum
+    shell  = dict(node_pos, node_normal, density)
+    bodies = dict(node_pos, node_normals, densities, centers, forces, torques
+             [, radii, velocities, angular_velocities]): with the last three,
+             points inside a body get its rigid motion (system.cpp:363-371)
+    """
+    u = _field("velocity", r_trg, eta, fiber=fiber, shell=shell, bodies=bodies)
+    if fiber is not None and fiber.get("self_stokeslets") is not None and fiber["r_src"].shape[0]:
+        _subtract_fiber_self(u, fiber["forces"] * fiber["weights"][:, None],
+                             fiber.get("fiber_sizes"), fiber["self_stokeslets"])
+    return u
 
 
 def velocity_gradient_at_targets(r_trg, eta, fiber=None, shell=None, bodies=None):
     """Gradient (n_trg, 3, 3) of velocity_at_targets' field, same dict
     inputs; the fiber self term is never subtracted (fiber_flow_grad)."""
-    g = _zero_grad(r_trg)
-    if fiber is not None:
-        g = g + fiber_flow_grad(fiber["r_src"], fiber["forces"], fiber["weights"], r_trg, eta)
-    if shell is not None:
-        g = g + periphery_flow_grad(shell["node_pos"], shell["node_normal"], shell["density"],
-                                    r_trg, eta)
-    if bodies is not None:
-        g = g + body_flow_grad(bodies["node_pos"], bodies["node_normals"], bodies["densities"],
-                               bodies["centers"], bodies["forces"], bodies["torques"], r_trg,
-                               eta)
-    return g
+    return _field("gradient", r_trg, eta, fiber=fiber, shell=shell, bodies=bodies)
 
 
 def vorticity_from_gradient(G):
@@ -205,92 +234,10 @@ def strain_rate_from_gradient(G):
     return 0.5 * (G + np.swapaxes(G, -1, -2))
 
 
-# ---------------------------------------------------------------------------
-# Pressure and stress. p is the Stokes pressure of the same fields (prefactor
-# 1/(4 pi), no eta dependence of its own; a rotlet's is zero), the stress is
-# sigma = -p I + eta (G + G^T) from p and the gradient kernels: two passes.
-# The pair kernels are reached through a system_fd backend's methods:
-# `backend=None` is HipBackend on r_trg's device (tensors in, tensors out, no
-# synchronization); any object with the same methods on numpy arrays serves
-# numpy inputs (the tests' closed forms).
-# ---------------------------------------------------------------------------
-
-def _compute(backend, r_trg):
-    if backend is not None:
-        return backend
-    from .system_fd import HipBackend
-    return HipBackend(r_trg.device)
-
-
-def _zero_rows(r_trg, *shape):
-    if torch.is_tensor(r_trg):
-        return torch.zeros((r_trg.shape[0],) + shape, dtype=r_trg.dtype, device=r_trg.device)
-    import numpy as np
-    return np.zeros((r_trg.shape[0],) + shape)
-
-
-def periphery_flow_pressure(node_pos, node_normal, density, r_trg, eta, backend=None):
-    """Pressure (n_trg,) of periphery_flow's field: the same
-    f_dl = 2*eta*n (x) density through the stresslet pressure kernel."""
-    if node_pos.shape[0] == 0:
-        return _zero_rows(r_trg)
-    return _compute(backend, r_trg).stresslet_normal_density_pressure(
-        node_pos, node_normal, density, r_trg, eta)
-
-
-def fiber_flow_pressure(r_src, fib_forces, weights, r_trg, backend=None):
-    """Pressure of fiber_flow's field without the self term (as
-    fiber_flow_grad)."""
-    if r_src.shape[0] == 0:
-        return _zero_rows(r_trg)
-    wf = fib_forces * weights[:, None]
-    return _compute(backend, r_trg).stokeslet_pressure(r_src, wf, r_trg)
-
-
-def body_flow_pressure(node_pos, node_normals, densities, centers, forces, torques, r_trg, eta,
-                       backend=None):
-    """Pressure of body_flow's field, term by term; the rotlet of the
-    torques has none."""
-    p = periphery_flow_pressure(node_pos, node_normals, densities, r_trg, eta, backend)
-    if centers.shape[0]:
-        p = p + _compute(backend, r_trg).stokeslet_pressure(centers, forces, r_trg)
-    return p
-
-
 def pressure_at_targets(r_trg, eta, fiber=None, shell=None, bodies=None, backend=None):
     """Pressure (n_trg,) of velocity_at_targets' field, same dict inputs; the
     fiber self term is never subtracted."""
-    p = _zero_rows(r_trg)
-    if fiber is not None:
-        p = p + fiber_flow_pressure(fiber["r_src"], fiber["forces"], fiber["weights"], r_trg,
-                                    backend)
-    if shell is not None:
-        p = p + periphery_flow_pressure(shell["node_pos"], shell["node_normal"],
-                                        shell["density"], r_trg, eta, backend)
-    if bodies is not None:
-        p = p + body_flow_pressure(bodies["node_pos"], bodies["node_normals"],
-                                   bodies["densities"], bodies["centers"], bodies["forces"],
-                                   bodies["torques"], r_trg, eta, backend)
-    return p
-
-
-def _gradient_through(backend, r_trg, eta, fiber, shell, bodies):
-    """velocity_gradient_at_targets' sum through a backend's `_grad` methods."""
-    g = _zero_rows(r_trg, 3, 3)
-    if fiber is not None and fiber["r_src"].shape[0]:
-        g = g + backend.stokeslet_grad(fiber["r_src"],
-                                       fiber["forces"] * fiber["weights"][:, None], r_trg, eta)
-    if shell is not None and shell["node_pos"].shape[0]:
-        g = g + backend.stresslet_normal_density_grad(
-            shell["node_pos"], shell["node_normal"], shell["density"], r_trg, eta)
-    if bodies is not None:
-        if bodies["node_pos"].shape[0]:
-            g = g + backend.stresslet_normal_density_grad(
-                bodies["node_pos"], bodies["node_normals"], bodies["densities"], r_trg, eta)
-        if bodies["centers"].shape[0]:
-            g = g + backend.stokeslet_grad(bodies["centers"], bodies["forces"], r_trg, eta)
-            g = g + backend.rotlet_grad(bodies["centers"], bodies["torques"], r_trg, eta)
-    return g
+    return _field("pressure", r_trg, eta, backend, fiber=fiber, shell=shell, bodies=bodies)
 
 
 def stress_from_fields(p, G, eta):
@@ -304,13 +251,12 @@ def stress_from_fields(p, G, eta):
 
 
 def stress_at_targets(r_trg, eta, fiber=None, shell=None, bodies=None, backend=None):
-    """Stress (n_trg, 3, 3) of velocity_at_targets' field: pressure_at_targets
-    and the velocity gradient of the same sources through stress_from_fields."""
-    backend = _compute(backend, r_trg)
-    G = _gradient_through(backend, r_trg, eta, fiber, shell, bodies)
-    p = pressure_at_targets(r_trg, eta, fiber=fiber, shell=shell, bodies=bodies,
-                            backend=backend)
-    return stress_from_fields(p, G, eta)
+    """Stress (n_trg, 3, 3) of velocity_at_targets' field: the velocity
+    gradient and the pressure of the same sources through stress_from_fields."""
+    sources = flow_sources(fiber, shell, bodies)
+    backend = backend if backend is not None else _default_backend(r_trg)
+    G = evaluate(sources, "gradient", r_trg, eta, backend)
+    return stress_from_fields(evaluate(sources, "pressure", r_trg, eta, backend), G, eta)
 
 
 def traction(stress, normals):
@@ -342,59 +288,40 @@ def surface_force_torque(points, normals, weights, stress, origin):
 # persistent kernel launch for all seeds (evaluator.trace_streamlines_device).
 # ---------------------------------------------------------------------------
 
-def streamline_source_sets(eta, fiber=None, shell=None, bodies=None, sources=None, to=None):
-    """The tracer's inputs from velocity_at_targets' terms: dict(stokeslet,
-    stresslet, rotlet, oseen = (r_src, strength) or None, background, bodies).
-
-    fiber, shell, bodies: the dicts of velocity_at_targets (fiber self terms
-    are never subtracted: the post-processing form). bodies may also carry
-    radii (n_b,), velocities (n_b, 3) and angular_velocities (n_b, 3): points
-    inside a body then move rigidly with it (system.cpp:363-371).
-    sources: dict with any of force_pos/forces (point forces, the regularized
-    Stokeslet), torque_pos/torques (point torques) and background =
-    (uniform, scale_factor, components).
+def streamline_source_sets(eta, fiber=None, shell=None, bodies=None, sources=None, to=None,
+                           flow=None):
+    """The tracer's inputs: the terms of flow_sources(fiber, shell, bodies,
+    sources), or of an already built `flow`, concatenated per kind:
+    dict(stokeslet, stresslet, rotlet, oseen = (r_src, strength) or None,
+    background, bodies = rows of (centre, radius, velocity, angular velocity)
+    or None). A double layer enters as its stresslet strength.
     `to` maps each array (numpy or tensor) to the tensor to concatenate."""
     to = to or (lambda a: a)
-    sl, dl, rot, os_ = [], [], [], []
-    if fiber is not None and fiber["r_src"].shape[0]:
-        sl.append((to(fiber["r_src"]), to(fiber["forces"]) * to(fiber["weights"])[:, None]))
-    if shell is not None and shell["node_pos"].shape[0]:
-        dl.append((to(shell["node_pos"]),
-                   double_layer_strength(to(shell["node_normal"]), to(shell["density"]), eta)))
-    rigid = None
-    if bodies is not None:
-        if bodies["node_pos"].shape[0]:
-            dl.append((to(bodies["node_pos"]),
-                       double_layer_strength(to(bodies["node_normals"]),
-                                             to(bodies["densities"]), eta)))
-        if bodies["centers"].shape[0]:
-            sl.append((to(bodies["centers"]), to(bodies["forces"])))
-            rot.append((to(bodies["centers"]), to(bodies["torques"])))
-            if bodies.get("radii") is not None:
-                rigid = torch.cat([to(bodies["centers"]), to(bodies["radii"]).reshape(-1, 1),
-                                   to(bodies["velocities"]), to(bodies["angular_velocities"])],
-                                  dim=1).contiguous()
-    background = None
-    if sources is not None:
-        if sources.get("forces") is not None and len(sources["forces"]):
-            os_.append((to(sources["force_pos"]), to(sources["forces"])))
-        if sources.get("torques") is not None and len(sources["torques"]):
-            rot.append((to(sources["torque_pos"]), to(sources["torques"])))
-        background = sources.get("background")
+    flow = flow if flow is not None else flow_sources(fiber, shell, bodies, sources)
 
-    def cat(parts):
+    def cat(kind, strength=lambda s: s):
+        parts = [(to(t[1]), strength(*map(to, t[2:]))) for t in flow.terms if t[0] == kind]
+        if kind == "rotlet":  # the tracer has the body centres before the point torques
+            parts.reverse()
         if not parts:
             return None
         return (torch.cat([p[0] for p in parts]).contiguous(),
                 torch.cat([p[1] for p in parts]).contiguous())
 
-    return dict(stokeslet=cat(sl), stresslet=cat(dl), rotlet=cat(rot), oseen=cat(os_),
-                background=background, bodies=rigid)
+    rigid = flow.bodies
+    if rigid is not None:
+        rigid = torch.cat([to(rigid["centers"]), to(rigid["radii"]).reshape(-1, 1),
+                           to(rigid["velocities"]), to(rigid["angular_velocities"])],
+                          dim=1).contiguous()
+    return dict(stokeslet=cat("stokeslet"),
+                stresslet=cat("double_layer", lambda n, d: double_layer_strength(n, d, eta)),
+                rotlet=cat("rotlet"), oseen=cat("oseen"), background=flow.background,
+                bodies=rigid)
 
 
 def streamlines_at_seeds(x0, eta, fiber=None, shell=None, bodies=None, sources=None,
                          dt_init=0.1, t_final=1.0, abs_err=1e-10, rel_err=1e-6,
-                         back_integrate=True, max_points=4096, backend=None):
+                         back_integrate=True, max_points=4096, backend=None, flow=None):
     """Streamlines of velocity_at_targets' field through every row of x0
     (n, 3), as StreamLine::compute (streamline.cpp:67-113) integrates them:
     adaptive Cash-Karp 5(4) from t = 0 to t_final, and to -t_final when
@@ -407,12 +334,12 @@ def streamlines_at_seeds(x0, eta, fiber=None, shell=None, bodies=None, sources=N
     evaluator.join_streamlines, val the velocity at its points, status 0 when
     t_final was reached both ways (else the tracer's code: 1 singularity,
     2 max_points recorded, 3 step control gave up). backend: a HipBackend
-    (default: one on x0's device, cuda:0 for numpy)."""
+    (default: one on x0's device, cuda:0 for numpy). flow: the already built
+    flow_sources.FlowSources, in place of the four dicts."""
     import numpy as np
     from .evaluator import join_streamlines
     if backend is None:
-        from .system_fd import HipBackend
-        backend = HipBackend(x0.device) if torch.is_tensor(x0) else HipBackend()
+        backend = _default_backend(x0)
 
     def to(a):
         if not torch.is_tensor(a):
@@ -423,7 +350,7 @@ def streamlines_at_seeds(x0, eta, fiber=None, shell=None, bodies=None, sources=N
     n = seeds.shape[0]
     if n == 0:
         return []
-    sets = streamline_source_sets(eta, fiber, shell, bodies, sources, to)
+    sets = streamline_source_sets(eta, fiber, shell, bodies, sources, to, flow)
     out = backend.trace_streamlines(
         seeds, eta, **sets, dt_init=dt_init, t_final=t_final, abs_err=abs_err, rel_err=rel_err,
         back_integrate=back_integrate, max_points=max_points)

@@ -196,145 +196,100 @@ def _body_sources(fibers, bodies):
     return nodes, normals, dens, centers, ft
 
 
-def velocity_field(frame, targets, eta, compute, shell_geometry=None,
-                   body_geometry=None, sources=None):
-    """System::velocity_at_targets (system.cpp:330-384) for fibers
-    (+shell/+bodies when geometry is given, +point/background sources when
-    `sources` = (PointSourceContainer|None, BackgroundSource|None) is
-    given; their clock is the frame time). compute: object with
-    stokeslet/stresslet_normal_density/rotlet (a system_fd backend)."""
-    targets = np.asarray(targets, float).reshape(-1, 3)
-    u = np.zeros((len(targets), 3))
+def streamline_terms(frame, eta, shell_geometry=None, body_geometry=None, sources=None):
+    """The frame as the dicts (fiber, shell, bodies, sources) that
+    flow_sources.flow_sources and flows.streamlines_at_seeds take: the one
+    step from a trajectory frame to the sources of its flow.
+    sources = (PointSourceContainer|None, BackgroundSource|None); their clock
+    is the frame time."""
+    terms = dict(fiber=None, shell=None, bodies=None, sources=None)
     if sources is not None:
         psc, bs = sources
-        if psc is not None:
-            u += psc.flow(targets, eta, float(frame.get("time", 0.0)), compute)
+        src = psc.live(float(frame.get("time", 0.0))) if psc is not None else {}
         if bs is not None and bs.is_active():
-            u += bs.flow(targets, eta)
+            src["background"] = (bs.uniform, bs.scale_factor, bs.components)
+        terms["sources"] = src
     fibers = fibers_from_frame(frame, eta)
     if fibers:
         r_src, wf = _fiber_sources(fibers)
         # fc_->flow(..., subtract_self=false), system.cpp:355
-        u += compute.stokeslet(r_src, wf, targets, eta)
+        terms["fiber"] = dict(r_src=r_src, forces=wf, weights=np.ones(len(wf)))
     dens = _shell_density(frame, shell_geometry)
     if dens is not None:
-        u += compute.stresslet_normal_density(
-            shell_geometry["nodes"], shell_geometry["normals"], dens,
-            targets, eta)
+        terms["shell"] = dict(node_pos=np.asarray(shell_geometry["nodes"], float),
+                              node_normal=np.asarray(shell_geometry["normals"], float),
+                              density=dens)
     bodies = bodies_from_frame(frame, body_geometry) \
         if body_geometry is not None else []
     if bodies:
         nodes, normals, dens, centers, ft = _body_sources(fibers, bodies)
-        u += compute.stresslet_normal_density(nodes, normals, dens, targets, eta)
-        u += compute.stokeslet(centers, ft[:, 0:3], targets, eta)
-        u += compute.rotlet(centers, ft[:, 3:6], targets, eta)
-        # points inside a body move rigidly (system.cpp:363-371)
-        for b in bodies:
-            dx = targets - b.position[None, :]
-            inside = np.linalg.norm(dx, axis=1) < b.radius
-            if inside.any():
-                u[inside] = b.velocity[None, :] + \
-                    np.cross(np.broadcast_to(b.angular_velocity, (int(inside.sum()), 3)),
-                             dx[inside])
-    return u
+        terms["bodies"] = dict(
+            node_pos=nodes, node_normals=normals, densities=dens, centers=centers,
+            forces=ft[:, 0:3], torques=ft[:, 3:6],
+            radii=np.array([b.radius for b in bodies], float),
+            velocities=np.stack([b.velocity for b in bodies]),
+            angular_velocities=np.stack([b.angular_velocity for b in bodies]))
+    return terms
+
+
+def frame_flow(frame, eta, shell_geometry=None, body_geometry=None, sources=None):
+    """The frame's flow_sources.FlowSources: what every field below evaluates.
+    Building it rebuilds the frame's fibers with their operators, so a caller
+    with several fields to evaluate builds it once and passes it as `flow`."""
+    from .flow_sources import flow_sources
+    return flow_sources(**streamline_terms(frame, eta, shell_geometry, body_geometry, sources))
+
+
+def _field(quantity, frame, targets, eta, compute, shell_geometry, body_geometry, sources, flow):
+    from .flow_sources import evaluate
+    if flow is None:
+        flow = frame_flow(frame, eta, shell_geometry, body_geometry, sources)
+    return evaluate(flow, quantity, np.asarray(targets, float).reshape(-1, 3), eta, compute)
+
+
+def velocity_field(frame, targets, eta, compute, shell_geometry=None,
+                   body_geometry=None, sources=None, flow=None):
+    """System::velocity_at_targets (system.cpp:330-384) for fibers
+    (+shell/+bodies when geometry is given, +point/background sources when
+    `sources` = (PointSourceContainer|None, BackgroundSource|None) is
+    given), or of an already built `flow` (frame_flow). Points inside a body
+    move rigidly with it. compute: a system_fd backend."""
+    return _field("velocity", frame, targets, eta, compute, shell_geometry, body_geometry,
+                  sources, flow)
 
 
 def velocity_gradient_field(frame, targets, eta, compute, shell_geometry=None,
-                            body_geometry=None, sources=None):
+                            body_geometry=None, sources=None, flow=None):
     """Analytic gradient (n, 3, 3), G[t, i, j] = du_i/dx_j, of velocity_field:
-    the same terms from the same sources, each through the backend's `_grad`
-    method. Inside a body the field is the rigid motion, so G is the rotation
-    matrix G_ij = eps_ikj omega_k there."""
-    targets = np.asarray(targets, float).reshape(-1, 3)
-    G = np.zeros((len(targets), 3, 3))
-    if sources is not None:
-        psc, bs = sources
-        if psc is not None:
-            G += psc.flow_grad(targets, eta, float(frame.get("time", 0.0)), compute)
-        if bs is not None and bs.is_active():
-            G += bs.flow_grad(targets)
-    fibers = fibers_from_frame(frame, eta)
-    if fibers:
-        r_src, wf = _fiber_sources(fibers)
-        G += compute.stokeslet_grad(r_src, wf, targets, eta)
-    dens = _shell_density(frame, shell_geometry)
-    if dens is not None:
-        G += compute.stresslet_normal_density_grad(
-            shell_geometry["nodes"], shell_geometry["normals"], dens,
-            targets, eta)
-    bodies = bodies_from_frame(frame, body_geometry) \
-        if body_geometry is not None else []
-    if bodies:
-        nodes, normals, dens, centers, ft = _body_sources(fibers, bodies)
-        G += compute.stresslet_normal_density_grad(nodes, normals, dens, targets, eta)
-        G += compute.stokeslet_grad(centers, ft[:, 0:3], targets, eta)
-        G += compute.rotlet_grad(centers, ft[:, 3:6], targets, eta)
-        for b in bodies:
-            dx = targets - b.position[None, :]
-            inside = np.linalg.norm(dx, axis=1) < b.radius
-            if inside.any():
-                w = b.angular_velocity
-                G[inside] = np.array([[0.0, -w[2], w[1]],
-                                      [w[2], 0.0, -w[0]],
-                                      [-w[1], w[0], 0.0]])
-    return G
-
-
-def _inside_any_body(targets, bodies):
-    inside = np.zeros(len(targets), bool)
-    for b in bodies:
-        inside |= np.linalg.norm(targets - b.position[None, :], axis=1) < b.radius
-    return inside
+    the same terms through the backend's `_grad` methods. Inside a body the
+    field is the rigid motion, so G is the rotation matrix
+    G_ij = eps_ikj omega_k there."""
+    return _field("gradient", frame, targets, eta, compute, shell_geometry, body_geometry,
+                  sources, flow)
 
 
 def pressure_field(frame, targets, eta, compute, shell_geometry=None,
-                   body_geometry=None, sources=None):
-    """Pressure (n,) of velocity_field: the same terms from the same sources,
-    each through the backend's `_pressure` method (the rotlets of the body
-    torques and of the point torques have none, the background flow is linear
-    and has a constant one, taken as 0). Inside a body the motion is rigid:
-    the fluid stress is 0 there and p is defined as 0."""
-    targets = np.asarray(targets, float).reshape(-1, 3)
-    p = np.zeros(len(targets))
-    if sources is not None:
-        psc, bs = sources
-        if psc is not None:
-            p += psc.flow_pressure(targets, float(frame.get("time", 0.0)), compute)
-        if bs is not None and bs.is_active():
-            p += bs.flow_pressure(targets)
-    fibers = fibers_from_frame(frame, eta)
-    if fibers:
-        r_src, wf = _fiber_sources(fibers)
-        p += compute.stokeslet_pressure(r_src, wf, targets)
-    dens = _shell_density(frame, shell_geometry)
-    if dens is not None:
-        p += compute.stresslet_normal_density_pressure(
-            shell_geometry["nodes"], shell_geometry["normals"], dens,
-            targets, eta)
-    bodies = bodies_from_frame(frame, body_geometry) \
-        if body_geometry is not None else []
-    if bodies:
-        nodes, normals, dens, centers, ft = _body_sources(fibers, bodies)
-        p += compute.stresslet_normal_density_pressure(nodes, normals, dens, targets, eta)
-        p += compute.stokeslet_pressure(centers, ft[:, 0:3], targets)
-        p[_inside_any_body(targets, bodies)] = 0.0
-    return p
+                   body_geometry=None, sources=None, flow=None):
+    """Pressure (n,) of velocity_field: the same terms through the backend's
+    `_pressure` methods (the rotlets of the body torques and of the point
+    torques have none, the background flow is linear and has a constant one,
+    taken as 0). Inside a body the motion is rigid: the fluid stress is 0
+    there and p is defined as 0."""
+    return _field("pressure", frame, targets, eta, compute, shell_geometry, body_geometry,
+                  sources, flow)
 
 
 def stress_field(frame, targets, eta, compute, shell_geometry=None,
-                 body_geometry=None, sources=None):
+                 body_geometry=None, sources=None, flow=None):
     """Stress (n, 3, 3) of velocity_field, sigma = -p I + eta (G + G^T) from
-    pressure_field and velocity_gradient_field. Inside a body the motion is
-    rigid (G antisymmetric, p = 0): sigma = 0 there."""
+    pressure_field and velocity_gradient_field of one flow. Inside a body the
+    motion is rigid (G antisymmetric, p = 0): sigma = 0 there."""
     from .flows import stress_from_fields
-    targets = np.asarray(targets, float).reshape(-1, 3)
-    args = (frame, targets, eta, compute, shell_geometry, body_geometry, sources)
-    sigma = stress_from_fields(pressure_field(*args), velocity_gradient_field(*args), eta)
-    bodies = bodies_from_frame(frame, body_geometry) \
-        if body_geometry is not None else []
-    if bodies:
-        sigma[_inside_any_body(targets, bodies)] = 0.0
-    return sigma
+    if flow is None:
+        flow = frame_flow(frame, eta, shell_geometry, body_geometry, sources)
+    return stress_from_fields(pressure_field(frame, targets, eta, compute, flow=flow),
+                              velocity_gradient_field(frame, targets, eta, compute, flow=flow),
+                              eta)
 
 
 def vorticity(field_fn, pts, eps=1e-7):
@@ -403,57 +358,19 @@ def integrate_streamline(field_fn, x0, dt_init=0.1, t_final=1.0, abs_err=1e-10,
     return {"x": x, "val": val, "time": t.tolist()}
 
 
-def streamline_terms(frame, eta, shell_geometry=None, body_geometry=None, sources=None):
-    """velocity_field's sources as the terms of flows.streamlines_at_seeds
-    (fiber, shell, bodies, sources), built once from the frame with the same
-    helpers."""
-    terms = dict(fiber=None, shell=None, bodies=None, sources=None)
-    if sources is not None:
-        psc, bs = sources
-        src = {}
-        if psc is not None:
-            time = float(frame.get("time", 0.0))
-            live = [p for p in psc.points if not (p.time_to_live and time >= p.time_to_live)]
-            forcers = [p for p in live if p.force.any()]
-            torquers = [p for p in live if p.torque.any()]
-            if forcers:
-                src["force_pos"] = np.stack([p.position for p in forcers])
-                src["forces"] = np.stack([p.force for p in forcers])
-            if torquers:
-                src["torque_pos"] = np.stack([p.position for p in torquers])
-                src["torques"] = np.stack([p.torque for p in torquers])
-        if bs is not None and bs.is_active():
-            src["background"] = (bs.uniform, bs.scale_factor, bs.components)
-        terms["sources"] = src
-    fibers = fibers_from_frame(frame, eta)
-    if fibers:
-        r_src, wf = _fiber_sources(fibers)
-        terms["fiber"] = dict(r_src=r_src, forces=wf, weights=np.ones(len(wf)))
-    dens = _shell_density(frame, shell_geometry)
-    if dens is not None:
-        terms["shell"] = dict(node_pos=np.asarray(shell_geometry["nodes"], float),
-                              node_normal=np.asarray(shell_geometry["normals"], float),
-                              density=dens)
-    bodies = bodies_from_frame(frame, body_geometry) \
-        if body_geometry is not None else []
-    if bodies:
-        nodes, normals, dens, centers, ft = _body_sources(fibers, bodies)
-        terms["bodies"] = dict(
-            node_pos=nodes, node_normals=normals, densities=dens, centers=centers,
-            forces=ft[:, 0:3], torques=ft[:, 3:6],
-            radii=np.array([b.radius for b in bodies], float),
-            velocities=np.stack([b.velocity for b in bodies]),
-            angular_velocities=np.stack([b.angular_velocity for b in bodies]))
-    return terms
+def _points(block, key):
+    """A request block's (n, 3) points under `key`; (0, 3) when it has none."""
+    x = eigen_decode((block or {}).get(key, []))
+    return np.asarray(x, float).reshape(-1, 3) if np.size(x) else np.zeros((0, 3))
 
 
-def _device_streamlines(frame, req, x0, eta, compute, shell_geometry, body_geometry, sources):
-    """The `"device": true` route of a streamlines request: the frame's
-    sources built once, all seeds traced by flows.streamlines_at_seeds.
-    Each line also carries the tracer's `status`."""
+def _device_streamlines(req, x0, eta, compute, flow):
+    """The `"device": true` route of a streamlines request: all seeds traced
+    by flows.streamlines_at_seeds. Each line also carries the tracer's
+    `status`."""
     from .flows import streamlines_at_seeds
     lines = streamlines_at_seeds(
-        x0, eta, **streamline_terms(frame, eta, shell_geometry, body_geometry, sources),
+        x0, eta, flow=flow,
         dt_init=float(req.get("dt_init", 0.1)), t_final=float(req.get("t_final", 1.0)),
         abs_err=float(req.get("abs_err", 1e-10)), rel_err=float(req.get("rel_err", 1e-6)),
         back_integrate=bool(req.get("back_integrate", True)),
@@ -463,28 +380,27 @@ def _device_streamlines(frame, req, x0, eta, compute, shell_geometry, body_geome
 
 
 def process_streamlines(frame, req, eta, compute, shell_geometry,
-                        vortex=False, body_geometry=None, sources=None):
+                        vortex=False, body_geometry=None, sources=None, flow=None):
     """process_streamlines / process_vortexlines (listener.cpp:51-74): one
     line per seed column; vortex=True integrates the curl field instead —
     the reference's central difference of the velocity, or, when the request
     map carries "analytic": true (an extension), the curl of
-    velocity_gradient_field."""
+    velocity_gradient_field. The frame's flow (frame_flow) is built once
+    for all right-hand sides, unless the caller passes it as `flow`."""
     req = req or {}
-    x0 = eigen_decode(req.get("x0", []))
-    x0 = np.asarray(x0, float).reshape(-1, 3) if np.size(x0) else np.zeros((0, 3))
+    x0 = _points(req, "x0")
     if not len(x0):
         return []
+    if flow is None:
+        flow = frame_flow(frame, eta, shell_geometry, body_geometry, sources)
     if req.get("device") and not vortex:
-        return _device_streamlines(frame, req, x0, eta, compute, shell_geometry,
-                                   body_geometry, sources)
-    field = lambda pts: velocity_field(frame, pts, eta, compute,
-                                       shell_geometry, body_geometry,
-                                       sources)
+        return _device_streamlines(req, x0, eta, compute, flow)
+    field = lambda pts: velocity_field(frame, pts, eta, compute, flow=flow)
     rhs_fn = None
     if vortex and req.get("analytic"):
         from .flows import vorticity_from_gradient
-        rhs_fn = lambda pts: vorticity_from_gradient(velocity_gradient_field(
-            frame, pts, eta, compute, shell_geometry, body_geometry, sources))
+        rhs_fn = lambda pts: vorticity_from_gradient(
+            velocity_gradient_field(frame, pts, eta, compute, flow=flow))
     elif vortex:
         rhs_fn = lambda pts: vorticity(field, pts)
     out = []
@@ -504,7 +420,8 @@ def process_streamlines(frame, req, eta, compute, shell_geometry,
 
 def serve(stdin, stdout, traj, compute, eta=1.0, shell_geometry=None,
           body_geometry=None, sources=None):
-    """The stdin/stdout request loop (listener.cpp:86-137)."""
+    """The stdin/stdout request loop (listener.cpp:86-137). The frame's flow
+    is built once per request, and only if some block carries points."""
     while True:
         raw = stdin.read(8)
         if len(raw) < 8:
@@ -525,47 +442,33 @@ def serve(stdin, stdout, traj, compute, eta=1.0, shell_geometry=None,
             stdout.flush()
             continue
         frame = traj.frames[frame_no]
-        vf = cmd.get("velocity_field", {}) or {}
-        x = eigen_decode(vf.get("x", []))
-        x = np.asarray(x, float).reshape(-1, 3) if np.size(x) else np.zeros((0, 3))
-        u = velocity_field(frame, x, eta, compute, shell_geometry,
-                           body_geometry, sources) \
-            if len(x) else np.zeros((0, 3))
+        blocks = (("velocity_field", "x"), ("streamlines", "x0"), ("vortexlines", "x0"),
+                  ("velocity_gradient", "x"), ("pressure", "x"), ("stress", "x"))
+        flow = frame_flow(frame, eta, shell_geometry, body_geometry, sources) \
+            if any(len(_points(cmd.get(block), key)) for block, key in blocks) else None
+
+        def field(fn, block, empty):
+            x = _points(cmd.get(block), "x")
+            return fn(frame, x, eta, compute, flow=flow) if len(x) else empty
+
+        u = field(velocity_field, "velocity_field", np.zeros((0, 3)))
         response = {
             "time": float(frame["time"]),
             "i_frame": frame_no,
             "n_frames": len(traj),
-            "streamlines": process_streamlines(frame, cmd.get("streamlines"),
-                                               eta, compute, shell_geometry,
-                                               body_geometry=body_geometry,
-                                               sources=sources),
-            "vortexlines": process_streamlines(frame, cmd.get("vortexlines"),
-                                               eta, compute, shell_geometry,
-                                               vortex=True,
-                                               body_geometry=body_geometry,
-                                               sources=sources),
+            "streamlines": process_streamlines(frame, cmd.get("streamlines"), eta, compute,
+                                               shell_geometry, flow=flow),
+            "vortexlines": process_streamlines(frame, cmd.get("vortexlines"), eta, compute,
+                                               shell_geometry, vortex=True, flow=flow),
             "velocity_field": eigen_encode_3xn(u),
         }
-        vg = cmd.get("velocity_gradient")
-        if vg:
-            xg = eigen_decode(vg.get("x", []))
-            xg = np.asarray(xg, float).reshape(-1, 3) if np.size(xg) \
-                else np.zeros((0, 3))
-            response["velocity_gradient"] = eigen_encode_9xn(
-                velocity_gradient_field(frame, xg, eta, compute, shell_geometry,
-                                        body_geometry, sources)
-                if len(xg) else np.zeros((0, 3, 3)))
-        for key, field, encode, empty in (
+        for key, fn, encode, empty in (
+                ("velocity_gradient", velocity_gradient_field, eigen_encode_9xn,
+                 np.zeros((0, 3, 3))),
                 ("pressure", pressure_field, eigen_encode_1xn, np.zeros(0)),
                 ("stress", stress_field, eigen_encode_9xn, np.zeros((0, 3, 3)))):
-            req = cmd.get(key)
-            if req:
-                xq = eigen_decode(req.get("x", []))
-                xq = np.asarray(xq, float).reshape(-1, 3) if np.size(xq) \
-                    else np.zeros((0, 3))
-                response[key] = encode(
-                    field(frame, xq, eta, compute, shell_geometry, body_geometry, sources)
-                    if len(xq) else empty)
+            if cmd.get(key):
+                response[key] = encode(field(fn, key, empty))
         out = msgpack.packb(response)
         stdout.write(struct.pack("<Q", len(out)))
         stdout.write(out)

@@ -36,55 +36,38 @@ class PointSourceContainer:
                                 time_to_live=t.get("time_to_live", 0.0))
                     for t in tables])
 
-    def flow(self, r_trg, eta, time, backend):
-        vel = np.zeros_like(np.asarray(r_trg, float))
+    def live(self, time):
+        """The sources alive at `time` as flow_sources' `sources` dict:
+        force_pos/forces of those with a force, torque_pos/torques of those
+        with a torque. time_to_live 0 means always alive, else a source is
+        dead from time >= time_to_live on (point_source.cpp:22-24)."""
         live = [p for p in self.points
                 if not (p.time_to_live and time >= p.time_to_live)]
-        forcers = [p for p in live if p.force.any()]
-        torquers = [p for p in live if p.torque.any()]
-        if forcers:
-            vel += backend.oseen_contract(
-                np.stack([p.position for p in forcers]),
-                np.asarray(r_trg, float),
-                np.stack([p.force for p in forcers]), eta)
-        if torquers:
-            vel += backend.rotlet(
-                np.stack([p.position for p in torquers]),
-                np.stack([p.torque for p in torquers]),
-                np.asarray(r_trg, float), eta)
-        return vel
+        out = {}
+        for pos, strength, attr in (("force_pos", "forces", "force"),
+                                    ("torque_pos", "torques", "torque")):
+            active = [p for p in live if getattr(p, attr).any()]
+            if active:
+                out[pos] = np.stack([p.position for p in active])
+                out[strength] = np.stack([getattr(p, attr) for p in active])
+        return out
+
+    def _field(self, quantity, r_trg, eta, time, backend):
+        from .flow_sources import evaluate, flow_sources
+        return evaluate(flow_sources(sources=self.live(time)), quantity,
+                        np.asarray(r_trg, float), eta, backend)
+
+    def flow(self, r_trg, eta, time, backend):
+        return self._field("velocity", r_trg, eta, time, backend)
 
     def flow_grad(self, r_trg, eta, time, backend):
-        """Velocity gradient (n_trg, 3, 3) of flow(): same liveness rules,
-        the backend's oseen_contract_grad / rotlet_grad."""
-        r_trg = np.asarray(r_trg, float)
-        grad = np.zeros((len(r_trg), 3, 3))
-        live = [p for p in self.points
-                if not (p.time_to_live and time >= p.time_to_live)]
-        forcers = [p for p in live if p.force.any()]
-        torquers = [p for p in live if p.torque.any()]
-        if forcers:
-            grad += backend.oseen_contract_grad(
-                np.stack([p.position for p in forcers]), r_trg,
-                np.stack([p.force for p in forcers]), eta)
-        if torquers:
-            grad += backend.rotlet_grad(
-                np.stack([p.position for p in torquers]),
-                np.stack([p.torque for p in torquers]), r_trg, eta)
-        return grad
+        """Velocity gradient (n_trg, 3, 3) of flow()."""
+        return self._field("gradient", r_trg, eta, time, backend)
 
     def flow_pressure(self, r_trg, time, backend):
-        """Pressure (n_trg,) of flow(): same liveness rules; the forces
-        through the backend's oseen_contract_pressure, the torques add
-        nothing (a rotlet's pressure is zero). No eta: no pressure reads it."""
-        r_trg = np.asarray(r_trg, float)
-        forcers = [p for p in self.points
-                   if not (p.time_to_live and time >= p.time_to_live) and p.force.any()]
-        if not forcers:
-            return np.zeros(len(r_trg))
-        return np.asarray(backend.oseen_contract_pressure(
-            np.stack([p.position for p in forcers]), r_trg,
-            np.stack([p.force for p in forcers])), float)
+        """Pressure (n_trg,) of flow(); the torques add nothing (a rotlet's
+        pressure is zero). No eta: no pressure of a point source reads it."""
+        return self._field("pressure", r_trg, None, time, backend)
 
 
 class BackgroundSource:
