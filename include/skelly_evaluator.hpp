@@ -218,14 +218,16 @@ struct StreamLine {
     int status = 0;
 };
 
-/* One joined line per column of x0 (3 x n_seeds): the backward path reversed
- * and without the seed it shares, then the forward path
+/* The two tracers' host entry points share one argument list. */
+using TraceHostFn = decltype(&skelly_trace_streamlines_host);
+
+/* One joined line per column of x0 (3 x n_seeds), traced by `entry`: the
+ * backward path reversed and without the seed it shares, then the forward path
  * (join_back_and_forward, streamline.cpp:56-65). */
-inline std::vector<StreamLine> trace_streamlines(const StreamlineField &f, const CMatrixRef &x0,
-                                                 double dt_init = 0.1, double t_final = 1.0,
-                                                 double abs_err = 1e-10, double rel_err = 1e-6,
-                                                 bool back_integrate = true,
-                                                 long max_points = 4096) {
+inline std::vector<StreamLine> trace_lines(TraceHostFn entry, const char *what,
+                                           const StreamlineField &f, const CMatrixRef &x0,
+                                           double dt_init, double t_final, double abs_err,
+                                           double rel_err, bool back_integrate, long max_points) {
     const long n = x0.size() / 3, n_jobs = n * (back_integrate ? 2 : 1);
     std::vector<double> x(3 * n_jobs * max_points), val(3 * n_jobs * max_points),
         t(n_jobs * max_points);
@@ -234,14 +236,14 @@ inline std::vector<StreamLine> trace_streamlines(const StreamlineField &f, const
                                   f.scale_factor[0], f.scale_factor[1], f.scale_factor[2],
                                   (double)f.components[0], (double)f.components[1],
                                   (double)f.components[2]};
-    check_rc(skelly_trace_streamlines_host(
+    check_rc(entry(
                  f.r_sl.ptr, f.f_sl.ptr, f.r_sl.size() / 3, f.r_dl.ptr, f.f_dl.ptr,
                  f.r_dl.size() / 3, f.r_rot.ptr, f.torques.ptr, f.r_rot.size() / 3, f.r_os.ptr,
                  f.f_os.ptr, f.r_os.size() / 3, f.has_background ? background : nullptr,
                  f.bodies.ptr, f.bodies.size() / 10, x0.ptr, n, back_integrate ? 1 : 0, f.eta,
                  f.reg, f.epsilon_distance, dt_init, t_final, abs_err, rel_err, max_points,
                  x.data(), t.data(), val.data(), count.data(), status.data()),
-             "trace_streamlines");
+             what);
     std::vector<StreamLine> lines(n);
     for (long i = 0; i < n; ++i) {
         const long back = back_integrate ? count[n + i] - 1 : 0; /* without the seed */
@@ -262,6 +264,29 @@ inline std::vector<StreamLine> trace_streamlines(const StreamlineField &f, const
         }
     }
     return lines;
+}
+
+inline std::vector<StreamLine> trace_streamlines(const StreamlineField &f, const CMatrixRef &x0,
+                                                 double dt_init = 0.1, double t_final = 1.0,
+                                                 double abs_err = 1e-10, double rel_err = 1e-6,
+                                                 bool back_integrate = true,
+                                                 long max_points = 4096) {
+    return trace_lines(skelly_trace_streamlines_host, "trace_streamlines", f, x0, dt_init,
+                       t_final, abs_err, rel_err, back_integrate, max_points);
+}
+
+/* Vortex lines (mirror of VortexLine::compute, streamline.cpp:115-165, with the
+ * analytic curl of the gradient kernels in place of its finite difference;
+ * skelly_trace_vortexlines_host): the lines of w = curl u of the same field,
+ * val the vorticity at their points, 2 w_b inside a body. The |u| > 1e3 stop
+ * (status 1) stays on the velocity, as the reference's observer has it. */
+inline std::vector<StreamLine> trace_vortexlines(const StreamlineField &f, const CMatrixRef &x0,
+                                                 double dt_init = 0.1, double t_final = 1.0,
+                                                 double abs_err = 1e-10, double rel_err = 1e-6,
+                                                 bool back_integrate = true,
+                                                 long max_points = 4096) {
+    return trace_lines(skelly_trace_vortexlines_host, "trace_vortexlines", f, x0, dt_init,
+                       t_final, abs_err, rel_err, back_integrate, max_points);
 }
 
 /* Mirror of the reference's string-keyed backend selection

@@ -317,6 +317,40 @@ int skelly_trace_streamlines_host(
     double dt_init, double t_final, double abs_err, double rel_err, long long max_points,
     double *x, double *t, double *val, int *count, int *status);
 
+/* ---- vortex lines ----
+ *
+ * The same tracer on the vorticity: dx/dt = w(x), w = curl u of the field
+ * above, summed analytically through the velocity-gradient kernels
+ * (skelly_stokeslet_grad_*, skelly_stresslet_grad_*, skelly_rotlet_grad_* and
+ * skelly_oseen_contract_grad_* with the same eta, reg, epsilon_distance) plus
+ * the constant curl of the background. A point inside a body has w = 2 w_b,
+ * the last such body deciding. Arguments, jobs, step control, outputs and
+ * the contract of the two forms are those of skelly_trace_streamlines_*, with
+ * two differences: val is the vorticity at each recorded point, and status 1
+ * is still a stop on the VELOCITY (|u| > 1e3 at a recorded point, evaluated
+ * there beside w, as the reference's observer does), so a line may run through
+ * a large vorticity and stops where a streamline would. */
+int skelly_trace_vortexlines_device(
+    const double *d_sl_r, const double *d_sl_f, long long n_sl,
+    const double *d_dl_r, const double *d_dl_f, long long n_dl,
+    const double *d_rot_r, const double *d_rot_f, long long n_rot,
+    const double *d_os_r, const double *d_os_f, long long n_os,
+    const double *background, const double *d_bodies, long long n_bodies,
+    const double *d_seeds, long long n_seeds, int back_integrate,
+    double eta, double reg, double epsilon_distance,
+    double dt_init, double t_final, double abs_err, double rel_err, long long max_points,
+    double *d_x, double *d_t, double *d_val, int *d_count, int *d_status, void *stream);
+int skelly_trace_vortexlines_host(
+    const double *sl_r, const double *sl_f, long long n_sl,
+    const double *dl_r, const double *dl_f, long long n_dl,
+    const double *rot_r, const double *rot_f, long long n_rot,
+    const double *os_r, const double *os_f, long long n_os,
+    const double *background, const double *bodies, long long n_bodies,
+    const double *seeds, long long n_seeds, int back_integrate,
+    double eta, double reg, double epsilon_distance,
+    double dt_init, double t_final, double abs_err, double rel_err, long long max_points,
+    double *x, double *t, double *val, int *count, int *status);
+
 /* Threads of a tracer workgroup: a compile-time constant of the library
  * (SKELLY_TRACE_BLOCK), for the record of a measurement. */
 int skelly_trace_block_size(void);

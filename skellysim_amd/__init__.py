@@ -41,6 +41,7 @@ from .evaluator import (  # noqa: F401
     stresslet_pressure_device,
     oseen_contract_pressure_device,
     trace_streamlines_device,
+    trace_vortexlines_device,
     join_streamlines,
 )
 from .sharded import ShardedPairEvaluator, shard_sizes, allgather_rows  # noqa: F401

@@ -64,13 +64,13 @@ PRESSURE_FAMILY = {
 
 
 class TraceCount(ctypes.c_longlong):
-    """The `long long` counts of the streamline entry points: a type of its
+    """The `long long` counts of the streamline and vortex-line entry points: a type of its
     own for the reason PressureCount is one (tests/test_streamlines_cpu.py
     checks these entry points' argument contract)."""
 
 
 def _trace_args(p, ip):
-    """skelly_trace_streamlines_*: p the double pointers, ip the int pointers.
+    """skelly_trace_streamlines_* and skelly_trace_vortexlines_*: p the double pointers, ip the int pointers.
     `background` is a host pointer in both forms."""
     t = TraceCount
     return ([p, p, t] * 4                       # sl, dl, rot, os: r, f, n
@@ -110,6 +110,8 @@ SIGNATURES = {
     "skelly_rsq_accuracy_probe": (_I, [_PV, _PV, _PV, _LL, _PV]),
     "skelly_trace_streamlines_host": (_I, _trace_args(_DP, ctypes.POINTER(_I))),
     "skelly_trace_streamlines_device": (_I, _trace_args(_PV, _PV) + [_PV]),
+    "skelly_trace_vortexlines_host": (_I, _trace_args(_DP, ctypes.POINTER(_I))),
+    "skelly_trace_vortexlines_device": (_I, _trace_args(_PV, _PV) + [_PV]),
     "skelly_trace_block_size": (_I, []),
 }
 for _name, _family in PAIR_FAMILY.items():

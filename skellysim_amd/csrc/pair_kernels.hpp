@@ -44,11 +44,14 @@ hipError_t launch_pair_kernel(PairKernel kernel, const double *r_src, const doub
 long long persistent_ws_bytes(hipStream_t stream);
 void release_persistent_ws(hipStream_t stream);
 
-/* One launch of the streamline tracer (streamline_kernel.hpp), asynchronous on
+/* One launch of the field-line tracer (streamline_kernel.hpp), asynchronous on
  * `stream`: the four source sets are packed into the stream's workspace and
  * every seed is integrated forward (and backward with back_integrate) by a
  * workgroup of its own. All pointers are device pointers. */
 struct TraceRequest {
+    /* 0: streamlines, dx/dt = u, val = u. Else vortex lines: dx/dt = curl u and
+     * val = curl u, the |u| > 1e3 stop still on the velocity. */
+    int vorticity;
     /* Stokeslet, Stresslet (9 doubles a source), Rotlet, OseenContract */
     const double *r[4], *f[4];
     long long n[4];

@@ -497,17 +497,23 @@ int skelly_oseen_tensor_batched_device(const double *d_pts, double *d_G, long lo
     return 0;
 }
 
-/* ---- streamlines ---- */
+} /* extern "C" */
 
-int skelly_trace_streamlines_device(
-    const double *d_sl_r, const double *d_sl_f, long long n_sl, const double *d_dl_r,
-    const double *d_dl_f, long long n_dl, const double *d_rot_r, const double *d_rot_f,
-    long long n_rot, const double *d_os_r, const double *d_os_f, long long n_os,
-    const double *background, const double *d_bodies, long long n_bodies, const double *d_seeds,
-    long long n_seeds, int back_integrate, double eta, double reg, double epsilon_distance,
-    double dt_init, double t_final, double abs_err, double rel_err, long long max_points,
-    double *d_x, double *d_t, double *d_val, int *d_count, int *d_status, void *stream) {
-    const char *where = "skelly_trace_streamlines_device";
+/* ---- streamlines and vortex lines ----
+ * One body for each form, shared by the two fields (TraceRequest::vorticity);
+ * the entry points below differ in the name they report and the field. */
+
+namespace {
+
+int trace_device(
+    const char *where, int vorticity, const double *d_sl_r, const double *d_sl_f, long long n_sl,
+    const double *d_dl_r, const double *d_dl_f, long long n_dl, const double *d_rot_r,
+    const double *d_rot_f, long long n_rot, const double *d_os_r, const double *d_os_f,
+    long long n_os, const double *background, const double *d_bodies, long long n_bodies,
+    const double *d_seeds, long long n_seeds, int back_integrate, double eta, double reg,
+    double epsilon_distance, double dt_init, double t_final, double abs_err, double rel_err,
+    long long max_points, double *d_x, double *d_t, double *d_val, int *d_count, int *d_status,
+    void *stream) {
     skelly::TraceRequest q;
     if (trace_request(where, q, d_sl_r, d_sl_f, n_sl, d_dl_r, d_dl_f, n_dl, d_rot_r, d_rot_f,
                       n_rot, d_os_r, d_os_f, n_os, background, d_bodies, n_bodies, d_seeds,
@@ -516,19 +522,19 @@ int skelly_trace_streamlines_device(
         return -1;
     if (n_seeds == 0)
         return 0;
+    q.vorticity = vorticity;
     CHK(where, skelly::launch_trace_streamlines(q, (hipStream_t)stream));
     return 0;
 }
 
-int skelly_trace_streamlines_host(
-    const double *sl_r, const double *sl_f, long long n_sl, const double *dl_r,
-    const double *dl_f, long long n_dl, const double *rot_r, const double *rot_f,
-    long long n_rot, const double *os_r, const double *os_f, long long n_os,
+int trace_host(
+    const char *where, int vorticity, const double *sl_r, const double *sl_f, long long n_sl,
+    const double *dl_r, const double *dl_f, long long n_dl, const double *rot_r,
+    const double *rot_f, long long n_rot, const double *os_r, const double *os_f, long long n_os,
     const double *background, const double *bodies, long long n_bodies, const double *seeds,
     long long n_seeds, int back_integrate, double eta, double reg, double epsilon_distance,
-    double dt_init, double t_final, double abs_err, double rel_err, long long max_points,
-    double *x, double *t, double *val, int *count, int *status) {
-    const char *where = "skelly_trace_streamlines_host";
+    double dt_init, double t_final, double abs_err, double rel_err, long long max_points, double *x,
+    double *t, double *val, int *count, int *status) {
     skelly::TraceRequest q;
     if (trace_request(where, q, sl_r, sl_f, n_sl, dl_r, dl_f, n_dl, rot_r, rot_f, n_rot, os_r,
                       os_f, n_os, background, bodies, n_bodies, seeds, n_seeds, back_integrate,
@@ -537,6 +543,7 @@ int skelly_trace_streamlines_host(
         return -1;
     if (n_seeds == 0)
         return 0;
+    q.vorticity = vorticity;
     const size_t n_jobs = (size_t)n_seeds * (back_integrate ? 2 : 1);
     const size_t rows = n_jobs * (size_t)max_points;
     /* one block for the call: the inputs, then x, val, t, count, status */
@@ -590,6 +597,68 @@ int skelly_trace_streamlines_host(
     CHK(where, err);
     CHK(where, sync);
     return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int skelly_trace_streamlines_device(
+    const double *d_sl_r, const double *d_sl_f, long long n_sl, const double *d_dl_r,
+    const double *d_dl_f, long long n_dl, const double *d_rot_r, const double *d_rot_f,
+    long long n_rot, const double *d_os_r, const double *d_os_f, long long n_os,
+    const double *background, const double *d_bodies, long long n_bodies, const double *d_seeds,
+    long long n_seeds, int back_integrate, double eta, double reg, double epsilon_distance,
+    double dt_init, double t_final, double abs_err, double rel_err, long long max_points,
+    double *d_x, double *d_t, double *d_val, int *d_count, int *d_status, void *stream) {
+    return trace_device("skelly_trace_streamlines_device", 0, d_sl_r, d_sl_f, n_sl, d_dl_r, d_dl_f,
+                        n_dl, d_rot_r, d_rot_f, n_rot, d_os_r, d_os_f, n_os, background, d_bodies,
+                        n_bodies, d_seeds, n_seeds, back_integrate, eta, reg, epsilon_distance,
+                        dt_init, t_final, abs_err, rel_err, max_points, d_x, d_t, d_val, d_count,
+                        d_status, stream);
+}
+
+int skelly_trace_streamlines_host(
+    const double *sl_r, const double *sl_f, long long n_sl, const double *dl_r, const double *dl_f,
+    long long n_dl, const double *rot_r, const double *rot_f, long long n_rot, const double *os_r,
+    const double *os_f, long long n_os, const double *background, const double *bodies,
+    long long n_bodies, const double *seeds, long long n_seeds, int back_integrate, double eta,
+    double reg, double epsilon_distance, double dt_init, double t_final, double abs_err,
+    double rel_err, long long max_points, double *x, double *t, double *val, int *count,
+    int *status) {
+    return trace_host("skelly_trace_streamlines_host", 0, sl_r, sl_f, n_sl, dl_r, dl_f, n_dl, rot_r,
+                      rot_f, n_rot, os_r, os_f, n_os, background, bodies, n_bodies, seeds, n_seeds,
+                      back_integrate, eta, reg, epsilon_distance, dt_init, t_final, abs_err,
+                      rel_err, max_points, x, t, val, count, status);
+}
+
+int skelly_trace_vortexlines_device(
+    const double *d_sl_r, const double *d_sl_f, long long n_sl, const double *d_dl_r,
+    const double *d_dl_f, long long n_dl, const double *d_rot_r, const double *d_rot_f,
+    long long n_rot, const double *d_os_r, const double *d_os_f, long long n_os,
+    const double *background, const double *d_bodies, long long n_bodies, const double *d_seeds,
+    long long n_seeds, int back_integrate, double eta, double reg, double epsilon_distance,
+    double dt_init, double t_final, double abs_err, double rel_err, long long max_points,
+    double *d_x, double *d_t, double *d_val, int *d_count, int *d_status, void *stream) {
+    return trace_device("skelly_trace_vortexlines_device", 1, d_sl_r, d_sl_f, n_sl, d_dl_r, d_dl_f,
+                        n_dl, d_rot_r, d_rot_f, n_rot, d_os_r, d_os_f, n_os, background, d_bodies,
+                        n_bodies, d_seeds, n_seeds, back_integrate, eta, reg, epsilon_distance,
+                        dt_init, t_final, abs_err, rel_err, max_points, d_x, d_t, d_val, d_count,
+                        d_status, stream);
+}
+
+int skelly_trace_vortexlines_host(
+    const double *sl_r, const double *sl_f, long long n_sl, const double *dl_r, const double *dl_f,
+    long long n_dl, const double *rot_r, const double *rot_f, long long n_rot, const double *os_r,
+    const double *os_f, long long n_os, const double *background, const double *bodies,
+    long long n_bodies, const double *seeds, long long n_seeds, int back_integrate, double eta,
+    double reg, double epsilon_distance, double dt_init, double t_final, double abs_err,
+    double rel_err, long long max_points, double *x, double *t, double *val, int *count,
+    int *status) {
+    return trace_host("skelly_trace_vortexlines_host", 1, sl_r, sl_f, n_sl, dl_r, dl_f, n_dl, rot_r,
+                      rot_f, n_rot, os_r, os_f, n_os, background, bodies, n_bodies, seeds, n_seeds,
+                      back_integrate, eta, reg, epsilon_distance, dt_init, t_final, abs_err,
+                      rel_err, max_points, x, t, val, count, status);
 }
 
 int skelly_trace_block_size(void) { return skelly::trace_block_size(); }

@@ -422,26 +422,11 @@ def _background9(background):
                            np.asarray(scale, np.float64).reshape(3), comp.astype(np.float64)])
 
 
-def trace_streamlines_device(seeds, eta, stokeslet=None, stresslet=None, rotlet=None, oseen=None,
-                             background=None, bodies=None, dt_init=0.1, t_final=1.0,
-                             abs_err=1e-10, rel_err=1e-6, back_integrate=True, max_points=4096,
-                             reg=5e-3, epsilon_distance=1e-5):
-    """Streamlines of the summed field from every row of `seeds` (n, 3), in
-    one kernel launch on torch's current stream (asynchronous, no
-    synchronization; skelly_trace_streamlines_device, include/skelly_hip.h).
-
-    stokeslet / stresslet / rotlet / oseen: (r_src (m, 3), strength (m, 3 or
-    9)) device tensors or None, the fields of stokeslet_device,
-    stresslet_device, rotlet_device and oseen_contract_device. background:
-    (uniform, scale_factor, components) host values, u_j += uniform_j +
-    x[components_j] * scale_factor_j. bodies: (n_b, 10) device tensor of rows
-    {centre, radius, velocity, angular velocity}; a point inside one moves
-    rigidly with it.
-
-    Returns a dict of device tensors per job (job j < n runs seed j forward,
-    job n + j backward when back_integrate): x (n_jobs, max_points, 3),
-    t (n_jobs, max_points), val as x (the velocity at the points), count and
-    status (n_jobs,) int32. Rows past count[job] are not written."""
+def _trace_lines_device(entry, seeds, eta, stokeslet, stresslet, rotlet, oseen, background,
+                        bodies, dt_init, t_final, abs_err, rel_err, back_integrate, max_points,
+                        reg, epsilon_distance):
+    """The two tracers' one body: `entry` names the library function
+    (skelly_<entry>), which decides the field."""
     import torch
     seeds = _dev_rows(seeds, 3, "seeds")
     args = []
@@ -469,15 +454,54 @@ def trace_streamlines_device(seeds, eta, stokeslet=None, stresslet=None, rotlet=
         "status": torch.empty((n_jobs,), dtype=torch.int32, device=seeds.device),
     }
     ptr = lambda t: None if t is None else _dptr(t)
-    rc = _native.lib().skelly_trace_streamlines_device(
+    rc = getattr(_native.lib(), f"skelly_{entry}")(
         *[a if isinstance(a, int) else ptr(a) for a in args],
         None if bg is None else _ptr(bg), ptr(bodies), 0 if bodies is None else bodies.shape[0],
         _dptr(seeds), n, int(bool(back_integrate)),
         float(eta), float(reg), float(epsilon_distance),
         float(dt_init), float(t_final), float(abs_err), float(rel_err), max_points,
         *[_dptr(out[k]) for k in ("x", "t", "val", "count", "status")], _stream_ptr())
-    _native.check(rc, "trace_streamlines_device")
+    _native.check(rc, entry)
     return out
+
+
+def trace_streamlines_device(seeds, eta, stokeslet=None, stresslet=None, rotlet=None, oseen=None,
+                             background=None, bodies=None, dt_init=0.1, t_final=1.0,
+                             abs_err=1e-10, rel_err=1e-6, back_integrate=True, max_points=4096,
+                             reg=5e-3, epsilon_distance=1e-5):
+    """Streamlines of the summed field from every row of `seeds` (n, 3), in
+    one kernel launch on torch's current stream (asynchronous, no
+    synchronization; skelly_trace_streamlines_device, include/skelly_hip.h).
+
+    stokeslet / stresslet / rotlet / oseen: (r_src (m, 3), strength (m, 3 or
+    9)) device tensors or None, the fields of stokeslet_device,
+    stresslet_device, rotlet_device and oseen_contract_device. background:
+    (uniform, scale_factor, components) host values, u_j += uniform_j +
+    x[components_j] * scale_factor_j. bodies: (n_b, 10) device tensor of rows
+    {centre, radius, velocity, angular velocity}; a point inside one moves
+    rigidly with it.
+
+    Returns a dict of device tensors per job (job j < n runs seed j forward,
+    job n + j backward when back_integrate): x (n_jobs, max_points, 3),
+    t (n_jobs, max_points), val as x (the velocity at the points), count and
+    status (n_jobs,) int32. Rows past count[job] are not written."""
+    return _trace_lines_device("trace_streamlines_device", seeds, eta, stokeslet, stresslet,
+                               rotlet, oseen, background, bodies, dt_init, t_final, abs_err,
+                               rel_err, back_integrate, max_points, reg, epsilon_distance)
+
+
+def trace_vortexlines_device(seeds, eta, stokeslet=None, stresslet=None, rotlet=None, oseen=None,
+                             background=None, bodies=None, dt_init=0.1, t_final=1.0,
+                             abs_err=1e-10, rel_err=1e-6, back_integrate=True, max_points=4096,
+                             reg=5e-3, epsilon_distance=1e-5):
+    """Vortex lines of the same field: trace_streamlines_device's arguments
+    and dict, with dx/dt and `val` the vorticity curl u, summed analytically
+    through the gradient kernels (skelly_trace_vortexlines_device). A point
+    inside a body has twice its angular velocity. Status 1 remains a stop on
+    the velocity, |u| > 1e3 at a recorded point."""
+    return _trace_lines_device("trace_vortexlines_device", seeds, eta, stokeslet, stresslet,
+                               rotlet, oseen, background, bodies, dt_init, t_final, abs_err,
+                               rel_err, back_integrate, max_points, reg, epsilon_distance)
 
 
 def join_streamlines(x, t, val, count, status, n_seeds):

@@ -336,6 +336,14 @@ def streamlines_at_seeds(x0, eta, fiber=None, shell=None, bodies=None, sources=N
     2 max_points recorded, 3 step control gave up). backend: a HipBackend
     (default: one on x0's device, cuda:0 for numpy). flow: the already built
     flow_sources.FlowSources, in place of the four dicts."""
+    return _lines_at_seeds("trace_streamlines", x0, eta, fiber, shell, bodies, sources, flow,
+                           backend, dt_init=dt_init, t_final=t_final, abs_err=abs_err,
+                           rel_err=rel_err, back_integrate=back_integrate, max_points=max_points)
+
+
+def _lines_at_seeds(trace, x0, eta, fiber, shell, bodies, sources, flow, backend, **control):
+    """streamlines_at_seeds and vortexlines_at_seeds: `trace` names the
+    backend's method."""
     import numpy as np
     from .evaluator import join_streamlines
     if backend is None:
@@ -351,11 +359,23 @@ def streamlines_at_seeds(x0, eta, fiber=None, shell=None, bodies=None, sources=N
     if n == 0:
         return []
     sets = streamline_source_sets(eta, fiber, shell, bodies, sources, to, flow)
-    out = backend.trace_streamlines(
-        seeds, eta, **sets, dt_init=dt_init, t_final=t_final, abs_err=abs_err, rel_err=rel_err,
-        back_integrate=back_integrate, max_points=max_points)
+    out = getattr(backend, trace)(seeds, eta, **sets, **control)
     host = {k: v.cpu().numpy() for k, v in out.items()}
     return join_streamlines(host["x"], host["t"], host["val"], host["count"], host["status"], n)
+
+
+def vortexlines_at_seeds(x0, eta, fiber=None, shell=None, bodies=None, sources=None,
+                         dt_init=0.1, t_final=1.0, abs_err=1e-10, rel_err=1e-6,
+                         back_integrate=True, max_points=4096, backend=None, flow=None):
+    """Vortex lines of the same field through every row of x0, as
+    VortexLine::compute (streamline.cpp:115-165) integrates them, with the
+    analytic curl of the gradient kernels in place of its finite difference:
+    dx/dt = curl u, still stopping where the VELOCITY has |u| > 1e3, as the
+    reference's observer does. Arguments and return as streamlines_at_seeds,
+    val the vorticity at the line's points (2 w inside a body)."""
+    return _lines_at_seeds("trace_vortexlines", x0, eta, fiber, shell, bodies, sources, flow,
+                           backend, dt_init=dt_init, t_final=t_final, abs_err=abs_err,
+                           rel_err=rel_err, back_integrate=back_integrate, max_points=max_points)
 
 
 class ShellOperator:

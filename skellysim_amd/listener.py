@@ -38,7 +38,11 @@ map traces all its seeds on the device in one kernel launch
 once, the reference's Cash-Karp 5(4) step control instead of scipy's RK45);
 each line then also carries the tracer's `status`, and `"max_points"` in the
 same map sizes its buffers (default 4096 points a direction). Vortex lines
-ignore the key."""
+ignore that key. `"tracer": "device"` is the spelling that both maps take: in
+`streamlines` it is a synonym of `"device": true`, and in `vortexlines` it
+traces all seeds on the device along the analytic curl
+(flows.vortexlines_at_seeds; `"analytic"` is then irrelevant), with `status`
+and `"max_points"` as for streamlines."""
 
 import argparse
 import os
@@ -364,12 +368,12 @@ def _points(block, key):
     return np.asarray(x, float).reshape(-1, 3) if np.size(x) else np.zeros((0, 3))
 
 
-def _device_streamlines(req, x0, eta, compute, flow):
-    """The `"device": true` route of a streamlines request: all seeds traced
-    by flows.streamlines_at_seeds. Each line also carries the tracer's
-    `status`."""
-    from .flows import streamlines_at_seeds
-    lines = streamlines_at_seeds(
+def _device_streamlines(req, x0, eta, compute, flow, vortex=False):
+    """The device route of a streamlines or vortexlines request: all seeds
+    traced by flows.streamlines_at_seeds or, vortex=True,
+    flows.vortexlines_at_seeds. Each line also carries the tracer's `status`."""
+    from . import flows
+    lines = (flows.vortexlines_at_seeds if vortex else flows.streamlines_at_seeds)(
         x0, eta, flow=flow,
         dt_init=float(req.get("dt_init", 0.1)), t_final=float(req.get("t_final", 1.0)),
         abs_err=float(req.get("abs_err", 1e-10)), rel_err=float(req.get("rel_err", 1e-6)),
@@ -386,13 +390,17 @@ def process_streamlines(frame, req, eta, compute, shell_geometry,
     the reference's central difference of the velocity, or, when the request
     map carries "analytic": true (an extension), the curl of
     velocity_gradient_field. The frame's flow (frame_flow) is built once
-    for all right-hand sides, unless the caller passes it as `flow`."""
+    for all right-hand sides, unless the caller passes it as `flow`.
+    "tracer": "device" in the map sends either kind to the device tracer, and
+    "device": true the streamlines alone (_device_streamlines)."""
     req = req or {}
     x0 = _points(req, "x0")
     if not len(x0):
         return []
     if flow is None:
         flow = frame_flow(frame, eta, shell_geometry, body_geometry, sources)
+    if req.get("tracer") == "device":
+        return _device_streamlines(req, x0, eta, compute, flow, vortex=vortex)
     if req.get("device") and not vortex:
         return _device_streamlines(req, x0, eta, compute, flow)
     field = lambda pts: velocity_field(frame, pts, eta, compute, flow=flow)

@@ -128,13 +128,24 @@ class HipBackend:
         rows: an empty set), `control` its step-control keywords. Returns its
         dict of per-job arrays, tensors (asynchronous) when `seeds` is one,
         else numpy."""
+        return self._trace("trace_streamlines_device", seeds, eta,
+                           (stokeslet, stresslet, rotlet, oseen), background, bodies, control)
+
+    def trace_vortexlines(self, seeds, eta, stokeslet=None, stresslet=None, rotlet=None,
+                          oseen=None, background=None, bodies=None, **control):
+        """evaluator.trace_vortexlines_device on this device; arguments and
+        return as trace_streamlines, `val` the vorticity."""
+        return self._trace("trace_vortexlines_device", seeds, eta,
+                           (stokeslet, stresslet, rotlet, oseen), background, bodies, control)
+
+    def _trace(self, entry, seeds, eta, pairs, background, bodies, control):
         import torch
         from . import evaluator
         sets = [None if p is None or len(p[0]) == 0 else (self._t(p[0]), self._t(p[1]))
-                for p in (stokeslet, stresslet, rotlet, oseen)]
+                for p in pairs]
         if bodies is not None:
             bodies = self._t(bodies) if len(bodies) else None
-        out = evaluator.trace_streamlines_device(
+        out = getattr(evaluator, entry)(
             self._t(seeds), eta, *sets, background=background, bodies=bodies, **control)
         if torch.is_tensor(seeds):
             return out

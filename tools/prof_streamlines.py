@@ -18,6 +18,13 @@ depends on the counts, not on the values.
           seconds. The route is a Python loop over the seeds, so its time is
           linear in their number.
 
+`--field vorticity` times the vortex lines instead: the device route is the
+`vortexlines` request with "tracer": "device" and its launch
+evaluator.trace_vortexlines_device, the streamline launch is timed beside it at
+the same shape (`streamline_launch_s`), and the host route is the
+`"analytic": true` one (a velocity_gradient_field and a velocity_field call per
+right-hand side).
+
 `--lib` loads another build of the library (the workgroup-size sweep builds
 it with EXTRA=-DSKELLY_TRACE_BLOCK=512 / 1024); the size in use is printed.
 Prints one JSON line per measurement and a markdown table (also written to
@@ -74,6 +81,8 @@ def main():
     p.add_argument("--host-budget", type=float, default=120.0)
     p.add_argument("--no-host", action="store_true",
                    help="device route only (the workgroup-size sweep)")
+    p.add_argument("--field", choices=["velocity", "vorticity"], default="velocity",
+                   help="streamlines (default) or vortex lines")
     p.add_argument("--seed", type=int, default=100)
     p.add_argument("--lib", default=None,
                    help="load this build of libskellyhip.so instead of the in-tree one")
@@ -102,10 +111,13 @@ def main():
     all_seeds = 0.5 * (lo + hi) + 0.25 * (hi - lo) * rng.uniform(-1, 1, (max(args.seeds), 3))
     request = {"dt_init": 0.1, "t_final": args.t_final, "abs_err": 1e-10, "rel_err": 1e-6,
                "back_integrate": True}
+    vortex = args.field == "vorticity"
+    device_key = {"tracer": "device"} if vortex else {"device": True}
+    trace = evaluator.trace_vortexlines_device if vortex else evaluator.trace_streamlines_device
     rows = []
 
     def emit(row):
-        row.update(block=block, fibers=args.fibers, nodes=args.nodes,
+        row.update(field=args.field, block=block, fibers=args.fibers, nodes=args.nodes,
                    shell_nodes=len(shell["nodes"]), t_final=args.t_final)
         rows.append(row)
         print(json.dumps(row), flush=True)
@@ -116,33 +128,43 @@ def main():
     sets = streamline_source_sets(1.0, to=to, **terms)
     for n in args.seeds:
         x0 = all_seeds[:n]
-        req = dict(request, x0=x0, device=True, max_points=args.max_points)
-        listener.process_streamlines(frame, req, 1.0, backend, shell)  # warm-up
+        req = dict(request, x0=x0, max_points=args.max_points, **device_key)
+        listener.process_streamlines(frame, req, 1.0, backend, shell, vortex=vortex)  # warm-up
         wall = []
         for _ in range(args.rounds):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            lines = listener.process_streamlines(frame, req, 1.0, backend, shell)
+            lines = listener.process_streamlines(frame, req, 1.0, backend, shell, vortex=vortex)
             wall.append(time.perf_counter() - t0)
         seeds_dev = to(x0)
-        kernel = []
-        for _ in range(args.rounds + 1):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            out = evaluator.trace_streamlines_device(
-                seeds_dev, 1.0, **sets, dt_init=0.1, t_final=args.t_final,
-                max_points=args.max_points)
-            e1.record()
-            e1.synchronize()
-            kernel.append(e0.elapsed_time(e1) * 1e-3)
-        kernel = kernel[1:]
+
+        def launches(fn):
+            """Device-event times of rounds launches after one warm-up, and the last result."""
+            took = []
+            for _ in range(args.rounds + 1):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                out = fn(seeds_dev, 1.0, **sets, dt_init=0.1, t_final=args.t_final,
+                         max_points=args.max_points)
+                e1.record()
+                e1.synchronize()
+                took.append(e0.elapsed_time(e1) * 1e-3)
+            return took[1:], out
+
+        kernel, out = launches(trace)
         count, status = out["count"].cpu().numpy(), out["status"].cpu().numpy()
-        emit({"route": "device", "seeds": n, "request_s": statistics.median(wall),
-              "request_s_min_max": [min(wall), max(wall)],
-              "launch_s": statistics.median(kernel), "launch_s_min_max": [min(kernel), max(kernel)],
-              "points": int(count.sum()), "points_max": int(count.max()),
-              "status": np.bincount(status, minlength=4).tolist(),
-              "line_points": [len(s["time"]) for s in lines[:4]]})
+        row = {"route": "device", "seeds": n, "request_s": statistics.median(wall),
+               "request_s_min_max": [min(wall), max(wall)],
+               "launch_s": statistics.median(kernel), "launch_s_min_max": [min(kernel), max(kernel)],
+               "points": int(count.sum()), "points_max": int(count.max()),
+               "status": np.bincount(status, minlength=4).tolist(),
+               "line_points": [len(s["time"]) for s in lines[:4]]}
+        if vortex:  # the streamline launch at the same shape, in the same run
+            other, out = launches(evaluator.trace_streamlines_device)
+            row.update(streamline_launch_s=statistics.median(other),
+                       streamline_launch_s_min_max=[min(other), max(other)],
+                       streamline_points=int(out["count"].sum().item()))
+        emit(row)
 
     # ---- host route -------------------------------------------------------------
     if not args.no_host:
@@ -158,9 +180,16 @@ def main():
                 f"{r['launch_s']:.4f} ({r['launch_s_min_max'][0]:.4f}-"
                 f"{r['launch_s_min_max'][1]:.4f}) | {r['points']} | "
                 f"{'/'.join(map(str, r['status']))} |")
+            if "streamline_launch_s" in r:
+                lo, hi = r["streamline_launch_s_min_max"]
+                lines.append(f"| device streamlines, launch alone | {r['seeds']} | | "
+                             f"{r['streamline_launch_s']:.4f} ({lo:.4f}-{hi:.4f}) | "
+                             f"{r['streamline_points']} | |")
         elif "request_s" in r:
-            lines.append(f"| host | {r['seeds']} | {r['request_s']:.2f} "
-                         f"({r['velocity_field_calls']} velocity_field calls) | | | |")
+            calls = f"{r['velocity_field_calls']} velocity_field calls"
+            if "velocity_gradient_field_calls" in r:
+                calls += f", {r['velocity_gradient_field_calls']} velocity_gradient_field calls"
+            lines.append(f"| host | {r['seeds']} | {r['request_s']:.2f} ({calls}) | | | |")
         elif "rhs_s" in r:
             lines.append(f"| host, one right-hand side | | {r['rhs_s']:.4f} | | | |")
         else:
@@ -175,32 +204,49 @@ def main():
 
 def host_route(args, frame, shell, backend, all_seeds, request, emit):
     from skellysim_amd import listener
+    vortex = args.field == "vorticity"
     one = all_seeds[:1]
-    listener.velocity_field(frame, one, 1.0, backend, shell)
+
+    def rhs_once():
+        listener.velocity_field(frame, one, 1.0, backend, shell)
+        if vortex:  # the analytic route: the curl's gradient, and the velocity for the stop
+            listener.velocity_gradient_field(frame, one, 1.0, backend, shell)
+    rhs_once()
     t0 = time.perf_counter()
     for _ in range(args.rhs_calls):
-        listener.velocity_field(frame, one, 1.0, backend, shell)
+        rhs_once()
     rhs = (time.perf_counter() - t0) / args.rhs_calls
-    emit({"route": "host", "what": "one right-hand side (velocity_field at 1 point)",
+    what = ("velocity_gradient_field and velocity_field at 1 point" if vortex
+            else "velocity_field at 1 point")
+    emit({"route": "host", "what": f"one right-hand side ({what})",
           "rhs_s": rhs, "rhs_calls": args.rhs_calls})
     if args.host_seeds and rhs * args.host_rhs_estimate * args.host_seeds <= args.host_budget:
-        calls = [0]
-        real = listener.velocity_field
+        calls = {"velocity_field": 0, "velocity_gradient_field": 0}
+        real = {name: getattr(listener, name) for name in calls}
 
-        def counted(*a, **k):
-            calls[0] += 1
-            return real(*a, **k)
-        listener.velocity_field = counted
+        def counted(name):
+            def call(*a, **k):
+                calls[name] += 1
+                return real[name](*a, **k)
+            return call
+        for name in calls:
+            setattr(listener, name, counted(name))
         try:
             t0 = time.perf_counter()
-            lines = listener.process_streamlines(
-                frame, dict(request, x0=all_seeds[:args.host_seeds]), 1.0, backend, shell)
+            req = dict(request, x0=all_seeds[:args.host_seeds])
+            if vortex:
+                req["analytic"] = True
+            lines = listener.process_streamlines(frame, req, 1.0, backend, shell, vortex=vortex)
             took = time.perf_counter() - t0
         finally:
-            listener.velocity_field = real
-        emit({"route": "host", "seeds": args.host_seeds, "request_s": took,
-              "velocity_field_calls": calls[0],
-              "line_points": [len(s["time"]) for s in lines[:4]]})
+            for name in calls:
+                setattr(listener, name, real[name])
+        row = {"route": "host", "seeds": args.host_seeds, "request_s": took,
+               "velocity_field_calls": calls["velocity_field"],
+               "line_points": [len(s["time"]) for s in lines[:4]]}
+        if vortex:
+            row["velocity_gradient_field_calls"] = calls["velocity_gradient_field"]
+        emit(row)
     else:
         emit({"route": "host", "what": "whole line not run: over --host-budget",
               "estimate_s_per_seed": rhs * args.host_rhs_estimate})
