@@ -1,6 +1,7 @@
-/* pair_kernels.hpp — the one seam between the kernel file (pair_kernels.hip)
- * and the C-ABI layer (skelly_hip.cpp). Both include it, so a changed
- * signature fails to compile instead of failing when the library loads. */
+/* pair_kernels.hpp — the seam between the C-ABI layer (skelly_hip.cpp) and the
+ * kernel units (pair_kernels.hip, trace_kernels.hip, probe_kernels.hip), and
+ * between those units. Each includes it, so a changed signature fails to
+ * compile instead of failing when the library loads. */
 
 #ifndef SKELLY_PAIR_KERNELS_HPP
 #define SKELLY_PAIR_KERNELS_HPP
@@ -9,7 +10,7 @@
 
 namespace skelly {
 
-/* The pair functors of pair_kernels.hip, by name. */
+/* The pair functors of pair_functors.hpp, by name. */
 enum class PairKernel {
     Stokeslet,
     Stresslet,
@@ -38,13 +39,13 @@ hipError_t launch_pair_kernel(PairKernel kernel, const double *r_src, const doub
                               const double *r_trg, double *out, long long n_src, long long n_trg,
                               double scale, double reg, double eps, hipStream_t stream);
 
-/* The persistent launch workspace of `stream` on the current device: its
- * capacity in bytes (0 without one), and its release with every block it
- * retired, for a stream that is idle and about to be destroyed. */
-long long persistent_ws_bytes(hipStream_t stream);
-void release_persistent_ws(hipStream_t stream);
+/* n_src sources as `kernel`'s packed records into `rec`, which holds
+ * rec_doubles<K>() * rec_count<K>(n_src) doubles (pair_functors.hpp):
+ * pack_sources<K>, asynchronous on `stream`. The tracer packs its sets here. */
+void launch_pack_sources(PairKernel kernel, const double *r_src, const double *f_src,
+                         long long n_src, double *rec, hipStream_t stream);
 
-/* One launch of the field-line tracer (streamline_kernel.hpp), asynchronous on
+/* One launch of the field-line tracer (trace_kernels.hip), asynchronous on
  * `stream`: the four source sets are packed into the stream's workspace and
  * every seed is integrated forward (and backward with back_integrate) by a
  * workgroup of its own. All pointers are device pointers. */
@@ -73,11 +74,13 @@ hipError_t launch_trace_streamlines(const TraceRequest &q, hipStream_t stream);
 /* Threads of a tracer workgroup (compile-time, SKELLY_TRACE_BLOCK). */
 int trace_block_size();
 
-/* Dense builders and the fp64 peak microbenchmark. */
+/* Dense builders (pair_kernels.hip). */
 hipError_t launch_oseen_tensor_batched(const double *pts, double *G, long long nf, long long n,
                                        double eta, double reg, double eps, hipStream_t stream);
 hipError_t launch_stresslet_times_normal(const double *pts, const double *normals, double *G,
                                          long long n, double reg, double eps, hipStream_t stream);
+
+/* Microbenchmarks and probes (probe_kernels.hip): the fp64 FMA peak. */
 hipError_t run_fp64_peak(double *out_tflops);
 /* out[3]: cost of a v_rsq_f64 and of a broadcast ds_read_b128 in v_fma_f64
  * issue slots, and the base run's TFLOP/s. */

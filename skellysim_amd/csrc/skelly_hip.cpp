@@ -18,6 +18,7 @@
 #include <mutex>
 #include <string>
 
+#include "launch_workspace.hpp"
 #include "pair_kernels.hpp"
 
 using skelly::PairKernel;
@@ -174,10 +175,11 @@ int pair_host(const char *where, PairKernel kernel, const double *r_src, const d
 double scale_stokes(double eta) { return kOneOver8Pi / eta; }          /* kernels.cu:59 */
 double scale_oseen(double eta) { return 1.0 / (8.0 * M_PI * eta); }    /* kernels.cpp:94,213 */
 
-/* The arguments of a streamline entry point as the launcher's request, after
- * the check that comes before any HIP call. True (message recorded) when a
- * count is negative. */
-bool trace_request(const char *where, skelly::TraceRequest &q, const double *sl_r,
+/* The arguments of a field-line entry point as the launcher's request (of
+ * streamlines, or of vortex lines with `vorticity`), after the check that
+ * comes before any HIP call. True (message recorded) when a count is negative.
+ * Each entry point names its 33 arguments here, once. */
+bool trace_request(const char *where, int vorticity, skelly::TraceRequest &q, const double *sl_r,
                    const double *sl_f, long long n_sl, const double *dl_r, const double *dl_f,
                    long long n_dl, const double *rot_r, const double *rot_f, long long n_rot,
                    const double *os_r, const double *os_f, long long n_os,
@@ -190,6 +192,7 @@ bool trace_request(const char *where, skelly::TraceRequest &q, const double *sl_
         negative_size(where, n_bodies, n_seeds) || negative_size(where, max_points))
         return true;
     q = skelly::TraceRequest{};
+    q.vorticity = vorticity;
     const double *r[4] = {sl_r, dl_r, rot_r, os_r}, *f[4] = {sl_f, dl_f, rot_f, os_f};
     const long long n[4] = {n_sl, n_dl, n_rot, n_os};
     for (int k = 0; k < 4; ++k) {
@@ -505,50 +508,25 @@ int skelly_oseen_tensor_batched_device(const double *d_pts, double *d_G, long lo
 
 namespace {
 
-int trace_device(
-    const char *where, int vorticity, const double *d_sl_r, const double *d_sl_f, long long n_sl,
-    const double *d_dl_r, const double *d_dl_f, long long n_dl, const double *d_rot_r,
-    const double *d_rot_f, long long n_rot, const double *d_os_r, const double *d_os_f,
-    long long n_os, const double *background, const double *d_bodies, long long n_bodies,
-    const double *d_seeds, long long n_seeds, int back_integrate, double eta, double reg,
-    double epsilon_distance, double dt_init, double t_final, double abs_err, double rel_err,
-    long long max_points, double *d_x, double *d_t, double *d_val, int *d_count, int *d_status,
-    void *stream) {
-    skelly::TraceRequest q;
-    if (trace_request(where, q, d_sl_r, d_sl_f, n_sl, d_dl_r, d_dl_f, n_dl, d_rot_r, d_rot_f,
-                      n_rot, d_os_r, d_os_f, n_os, background, d_bodies, n_bodies, d_seeds,
-                      n_seeds, back_integrate, eta, reg, epsilon_distance, dt_init, t_final,
-                      abs_err, rel_err, max_points, d_x, d_t, d_val, d_count, d_status))
-        return -1;
-    if (n_seeds == 0)
+/* Device form: q as trace_request() made it, launched on the caller's stream. */
+int trace_device(const char *where, const skelly::TraceRequest &q, void *stream) {
+    if (q.n_seeds == 0)
         return 0;
-    q.vorticity = vorticity;
     CHK(where, skelly::launch_trace_streamlines(q, (hipStream_t)stream));
     return 0;
 }
 
-int trace_host(
-    const char *where, int vorticity, const double *sl_r, const double *sl_f, long long n_sl,
-    const double *dl_r, const double *dl_f, long long n_dl, const double *rot_r,
-    const double *rot_f, long long n_rot, const double *os_r, const double *os_f, long long n_os,
-    const double *background, const double *bodies, long long n_bodies, const double *seeds,
-    long long n_seeds, int back_integrate, double eta, double reg, double epsilon_distance,
-    double dt_init, double t_final, double abs_err, double rel_err, long long max_points, double *x,
-    double *t, double *val, int *count, int *status) {
-    skelly::TraceRequest q;
-    if (trace_request(where, q, sl_r, sl_f, n_sl, dl_r, dl_f, n_dl, rot_r, rot_f, n_rot, os_r,
-                      os_f, n_os, background, bodies, n_bodies, seeds, n_seeds, back_integrate,
-                      eta, reg, epsilon_distance, dt_init, t_final, abs_err, rel_err, max_points,
-                      x, t, val, count, status))
-        return -1;
-    if (n_seeds == 0)
+/* Host form: q's inputs are host arrays and x, t, val, count, status the
+ * caller's outputs; upload, launch, download, sync on the library's stream. */
+int trace_host(const char *where, skelly::TraceRequest q, double *x, double *t, double *val,
+               int *count, int *status) {
+    if (q.n_seeds == 0)
         return 0;
-    q.vorticity = vorticity;
-    const size_t n_jobs = (size_t)n_seeds * (back_integrate ? 2 : 1);
-    const size_t rows = n_jobs * (size_t)max_points;
+    const size_t n_jobs = (size_t)q.n_seeds * (q.back_integrate ? 2 : 1);
+    const size_t rows = n_jobs * (size_t)q.max_points;
     /* one block for the call: the inputs, then x, val, t, count, status */
     const int width[4] = {3, 9, 3, 3};
-    size_t in_doubles = (size_t)n_bodies * 10 + (size_t)n_seeds * 3;
+    size_t in_doubles = (size_t)q.n_bodies * 10 + (size_t)q.n_seeds * 3;
     for (int k = 0; k < 4; ++k)
         in_doubles += (size_t)q.n[k] * (3 + width[k]);
     const size_t bytes = (in_doubles + rows * 7) * 8 + n_jobs * 2 * sizeof(int);
@@ -571,8 +549,8 @@ int trace_host(
         upload(q.r[k], (size_t)q.n[k] * 3);
         upload(q.f[k], (size_t)q.n[k] * width[k]);
     }
-    upload(q.bodies, (size_t)n_bodies * 10);
-    upload(q.seeds, (size_t)n_seeds * 3);
+    upload(q.bodies, (size_t)q.n_bodies * 10);
+    upload(q.seeds, (size_t)q.n_seeds * 3);
     q.x = at;
     q.val = q.x + rows * 3;
     q.t = q.val + rows * 3;
@@ -611,11 +589,14 @@ int skelly_trace_streamlines_device(
     long long n_seeds, int back_integrate, double eta, double reg, double epsilon_distance,
     double dt_init, double t_final, double abs_err, double rel_err, long long max_points,
     double *d_x, double *d_t, double *d_val, int *d_count, int *d_status, void *stream) {
-    return trace_device("skelly_trace_streamlines_device", 0, d_sl_r, d_sl_f, n_sl, d_dl_r, d_dl_f,
-                        n_dl, d_rot_r, d_rot_f, n_rot, d_os_r, d_os_f, n_os, background, d_bodies,
-                        n_bodies, d_seeds, n_seeds, back_integrate, eta, reg, epsilon_distance,
-                        dt_init, t_final, abs_err, rel_err, max_points, d_x, d_t, d_val, d_count,
-                        d_status, stream);
+    const char *where = "skelly_trace_streamlines_device";
+    skelly::TraceRequest q;
+    if (trace_request(where, 0, q, d_sl_r, d_sl_f, n_sl, d_dl_r, d_dl_f, n_dl, d_rot_r, d_rot_f,
+                      n_rot, d_os_r, d_os_f, n_os, background, d_bodies, n_bodies, d_seeds,
+                      n_seeds, back_integrate, eta, reg, epsilon_distance, dt_init, t_final,
+                      abs_err, rel_err, max_points, d_x, d_t, d_val, d_count, d_status))
+        return -1;
+    return trace_device(where, q, stream);
 }
 
 int skelly_trace_streamlines_host(
@@ -626,10 +607,14 @@ int skelly_trace_streamlines_host(
     double reg, double epsilon_distance, double dt_init, double t_final, double abs_err,
     double rel_err, long long max_points, double *x, double *t, double *val, int *count,
     int *status) {
-    return trace_host("skelly_trace_streamlines_host", 0, sl_r, sl_f, n_sl, dl_r, dl_f, n_dl, rot_r,
-                      rot_f, n_rot, os_r, os_f, n_os, background, bodies, n_bodies, seeds, n_seeds,
-                      back_integrate, eta, reg, epsilon_distance, dt_init, t_final, abs_err,
-                      rel_err, max_points, x, t, val, count, status);
+    const char *where = "skelly_trace_streamlines_host";
+    skelly::TraceRequest q;
+    if (trace_request(where, 0, q, sl_r, sl_f, n_sl, dl_r, dl_f, n_dl, rot_r, rot_f, n_rot, os_r,
+                      os_f, n_os, background, bodies, n_bodies, seeds, n_seeds, back_integrate,
+                      eta, reg, epsilon_distance, dt_init, t_final, abs_err, rel_err, max_points,
+                      x, t, val, count, status))
+        return -1;
+    return trace_host(where, q, x, t, val, count, status);
 }
 
 int skelly_trace_vortexlines_device(
@@ -640,11 +625,14 @@ int skelly_trace_vortexlines_device(
     long long n_seeds, int back_integrate, double eta, double reg, double epsilon_distance,
     double dt_init, double t_final, double abs_err, double rel_err, long long max_points,
     double *d_x, double *d_t, double *d_val, int *d_count, int *d_status, void *stream) {
-    return trace_device("skelly_trace_vortexlines_device", 1, d_sl_r, d_sl_f, n_sl, d_dl_r, d_dl_f,
-                        n_dl, d_rot_r, d_rot_f, n_rot, d_os_r, d_os_f, n_os, background, d_bodies,
-                        n_bodies, d_seeds, n_seeds, back_integrate, eta, reg, epsilon_distance,
-                        dt_init, t_final, abs_err, rel_err, max_points, d_x, d_t, d_val, d_count,
-                        d_status, stream);
+    const char *where = "skelly_trace_vortexlines_device";
+    skelly::TraceRequest q;
+    if (trace_request(where, 1, q, d_sl_r, d_sl_f, n_sl, d_dl_r, d_dl_f, n_dl, d_rot_r, d_rot_f,
+                      n_rot, d_os_r, d_os_f, n_os, background, d_bodies, n_bodies, d_seeds,
+                      n_seeds, back_integrate, eta, reg, epsilon_distance, dt_init, t_final,
+                      abs_err, rel_err, max_points, d_x, d_t, d_val, d_count, d_status))
+        return -1;
+    return trace_device(where, q, stream);
 }
 
 int skelly_trace_vortexlines_host(
@@ -655,10 +643,14 @@ int skelly_trace_vortexlines_host(
     double reg, double epsilon_distance, double dt_init, double t_final, double abs_err,
     double rel_err, long long max_points, double *x, double *t, double *val, int *count,
     int *status) {
-    return trace_host("skelly_trace_vortexlines_host", 1, sl_r, sl_f, n_sl, dl_r, dl_f, n_dl, rot_r,
-                      rot_f, n_rot, os_r, os_f, n_os, background, bodies, n_bodies, seeds, n_seeds,
-                      back_integrate, eta, reg, epsilon_distance, dt_init, t_final, abs_err,
-                      rel_err, max_points, x, t, val, count, status);
+    const char *where = "skelly_trace_vortexlines_host";
+    skelly::TraceRequest q;
+    if (trace_request(where, 1, q, sl_r, sl_f, n_sl, dl_r, dl_f, n_dl, rot_r, rot_f, n_rot, os_r,
+                      os_f, n_os, background, bodies, n_bodies, seeds, n_seeds, back_integrate,
+                      eta, reg, epsilon_distance, dt_init, t_final, abs_err, rel_err, max_points,
+                      x, t, val, count, status))
+        return -1;
+    return trace_host(where, q, x, t, val, count, status);
 }
 
 int skelly_trace_block_size(void) { return skelly::trace_block_size(); }

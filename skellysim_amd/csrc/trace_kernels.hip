@@ -1,12 +1,14 @@
-/* streamline_kernel.hpp — the field-line tracer: one persistent workgroup per
+/* trace_kernels.hip — the field-line tracer: one persistent workgroup per
  * job integrates dx/dt = u(x) (streamlines) or dx/dt = curl u(x) (vortex
  * lines) with adaptive Cash-Karp 5(4), every field evaluation, step decision
  * and record inside the one launch.
  *
- * Included by pair_kernels.hip (and by nothing else) behind its functors,
- * pack_sources and the workspace: the field is summed with the functors'
- * own K::pair<true> / K::finish over records that pack_sources<K> wrote, so
- * the per-pair arithmetic is the tested one.
+ * A translation unit of its own over pair_functors.hpp: the field is summed
+ * with the functors' own K::pair<true> / K::finish, with the Params that
+ * launch_params<K> gives a pair launch, over records that pack_sources<K>
+ * wrote (launch_pack_sources of pair_kernels.hip, so that kernel exists once),
+ * so the per-pair arithmetic is the tested one. The workspace is the pair
+ * launches' (launch_workspace.hpp).
  *
  * A job is one seed in one direction (a seed traced both ways is two jobs);
  * jobs share nothing but the read-only records, so there is no grid-wide seam
@@ -22,7 +24,7 @@
  * inside a body (|x - c_b| < radius_b) moves rigidly, U_b + w_b x (x - c_b),
  * later bodies overwriting earlier ones.
  *
- * Vorticity (trace_vorticity, the field of a vortex line): the curl of the
+ * Vorticity (TRACE_VORTICITY, the field of a vortex line): the curl of the
  * same field. Each set goes through its gradient functor (StokesletGrad for
  * the Stokeslets and, with reg and eps, for the regularized point forces;
  * StressletGrad; RotletGrad), and each thread takes the curl
@@ -65,6 +67,14 @@
  * or more than 4 * max_points + 1000 tries in all). count stays at the -1 the
  * host wrote for a job that never ran. */
 
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "launch_workspace.hpp"
+#include "pair_functors.hpp"
+#include "pair_kernels.hpp"
+
 #ifndef SKELLY_TRACE_BLOCK
 #define SKELLY_TRACE_BLOCK 256 /* profiles/streamlines.md */
 #endif
@@ -106,26 +116,65 @@ struct TraceJobs {
     int *count, *status; /* (n_jobs) */
 };
 
-/* This thread's share of one set: records tid, tid + B, ... onto the point x,
- * finished (scaled), added to u. */
-template <typename K, int B>
-__device__ __forceinline__ void trace_add_set(const double *__restrict__ rec, const long long n,
-                                              const double (&x)[3],
-                                              const typename K::Params &params, double (&u)[3]) {
+/* A set's finished (scaled) partial velocity, added to u. */
+template <typename K>
+__device__ __forceinline__ void trace_finish(const double (&acc)[3],
+                                             const typename K::Params &params, double (&u)[3]) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+        u[j] += K::finish(acc[j], params);
+}
+
+/* The curl of a set's finished partial gradient, added to w. */
+template <typename K>
+__device__ __forceinline__ void trace_finish(const double (&acc)[9],
+                                             const typename K::Params &params, double (&w)[3]) {
+    w[0] += K::finish(acc[7], params) - K::finish(acc[5], params);
+    w[1] += K::finish(acc[2], params) - K::finish(acc[6], params);
+    w[2] += K::finish(acc[3], params) - K::finish(acc[1], params);
+}
+
+/* This thread's share of one set through the functor K: records tid, tid + B,
+ * ... of a buffer with STRIDE doubles a record onto the point x, finished by
+ * the trace_finish of K's OUTDIM and added to part. The accumulators are the
+ * walk's own locals: handed in by the caller they get other registers (as
+ * many), and the kernels are no longer the bytes that were measured
+ * (profiles/csrc_layout.md). */
+template <typename K, int STRIDE, int B>
+__device__ __forceinline__ void trace_walk(const double *__restrict__ rec, const long long n,
+                                           const double (&x)[3],
+                                           const typename K::Params &params,
+                                           double (&part)[3]) {
     constexpr int R = rec_doubles<K>();
-    double acc[3] = {0.0, 0.0, 0.0};
+    double acc[K::OUTDIM];
+#pragma unroll
+    for (int j = 0; j < K::OUTDIM; ++j)
+        acc[j] = 0.0;
     unsigned zmin = ~0u;
     for (long long s = threadIdx.x; s < n; s += B) {
-        const double *__restrict__ p = rec + R * s;
+        const double *__restrict__ p = rec + STRIDE * s;
         double v[R];
 #pragma unroll
         for (int i = 0; i < R; ++i)
             v[i] = p[i];
         K::template pair<true>(x, v, v + 3, v + 3 + K::SRCDIM, acc, params, zmin);
     }
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-        u[j] += K::finish(acc[j], params);
+    trace_finish<K>(acc, params, part);
+}
+
+/* This thread's share of one set, added to part: through the velocity functor
+ * V for the velocity, through the gradient functor G for the vorticity. G
+ * walks V's records (same {r, f} prefix) at V's stride. */
+template <int FIELD, typename V, typename G, int B>
+__device__ __forceinline__ void trace_add_set(const double *__restrict__ rec, const long long n,
+                                              const double (&x)[3],
+                                              const typename V::Params &pv,
+                                              const typename G::Params &pg, double (&part)[3]) {
+    static_assert(G::SRCDIM == V::SRCDIM && G::AUXDIM == 0, "G reads the prefix of V's record");
+    if constexpr (FIELD == TRACE_VORTICITY)
+        trace_walk<G, rec_doubles<V>(), B>(rec, n, x, pg, part);
+    else
+        trace_walk<V, rec_doubles<V>(), B>(rec, n, x, pv, part);
 }
 
 /* The workgroup's sum of every thread's part, the same bits in every thread.
@@ -173,99 +222,54 @@ __device__ __forceinline__ int trace_body_at(const TraceField &f, const double (
     return __builtin_amdgcn_readfirstlane(inside);
 }
 
-/* u(x), the same bits in every thread of the workgroup. `red` is the
+/* The field that instantiation FIELD integrates and records, u(x) or
+ * curl u(x), the same bits in every thread of the workgroup. `red` is the
  * workgroup's [2][B / 64][3] LDS block and `phase` its evaluation counter.
  * Must be called by all threads with the same x (uniform control flow). */
+template <int B, int FIELD>
+__device__ __forceinline__ void trace_rhs(const TraceField &f, const double (&x)[3],
+                                          double (*red)[B / 64][3], int &phase, double (&k)[3]) {
+    /* rigid motion inside a body: U_b + w_b x (x - c_b), whose curl is 2 w_b */
+    const int inside = trace_body_at(f, x);
+    if (inside >= 0) {
+        const double *q = f.bodies + SKELLY_TRACE_BODY_DOUBLES * inside;
+        if constexpr (FIELD == TRACE_VORTICITY) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                k[j] = 2.0 * q[7 + j];
+        } else {
+            const double dx = x[0] - q[0], dy = x[1] - q[1], dz = x[2] - q[2];
+            k[0] = q[4] + (q[8] * dz - q[9] * dy);
+            k[1] = q[5] + (q[9] * dx - q[7] * dz);
+            k[2] = q[6] + (q[7] * dy - q[8] * dx);
+        }
+        return;
+    }
+
+    /* the regularized point forces go through StokesletGrad with reg and eps */
+    double part[3] = {0.0, 0.0, 0.0};
+    trace_add_set<FIELD, Stokeslet, StokesletGrad, B>(f.rec[0], f.n[0], x, f.sl, f.gsl, part);
+    trace_add_set<FIELD, Stresslet, StressletGrad, B>(f.rec[1], f.n[1], x, f.dl, f.gdl, part);
+    trace_add_set<FIELD, Rotlet, RotletGrad, B>(f.rec[2], f.n[2], x, f.rot, f.grot, part);
+    trace_add_set<FIELD, OseenContract, StokesletGrad, B>(f.rec[3], f.n[3], x, f.os, f.gos, part);
+
+    double sum[3];
+    trace_reduce<B>(part, red, phase, sum);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        if constexpr (FIELD == TRACE_VORTICITY)
+            k[j] = sum[j] + f.bg_curl[j];
+        else
+            k[j] = sum[j] + (f.uniform[j] + x[f.components[j]] * f.bg_scale[j]);
+    }
+}
+
+/* u(x), for the singularity stop of every FIELD. */
 template <int B>
 __device__ __forceinline__ void trace_field(const TraceField &f, const double (&x)[3],
                                             double (*red)[B / 64][3], int &phase,
                                             double (&u)[3]) {
-    /* rigid motion inside a body */
-    const int inside = trace_body_at(f, x);
-    if (inside >= 0) {
-        const double *q = f.bodies + SKELLY_TRACE_BODY_DOUBLES * inside;
-        const double dx = x[0] - q[0], dy = x[1] - q[1], dz = x[2] - q[2];
-        u[0] = q[4] + (q[8] * dz - q[9] * dy);
-        u[1] = q[5] + (q[9] * dx - q[7] * dz);
-        u[2] = q[6] + (q[7] * dy - q[8] * dx);
-        return;
-    }
-
-    double part[3] = {0.0, 0.0, 0.0};
-    trace_add_set<Stokeslet, B>(f.rec[0], f.n[0], x, f.sl, part);
-    trace_add_set<Stresslet, B>(f.rec[1], f.n[1], x, f.dl, part);
-    trace_add_set<Rotlet, B>(f.rec[2], f.n[2], x, f.rot, part);
-    trace_add_set<OseenContract, B>(f.rec[3], f.n[3], x, f.os, part);
-
-    double sum[3];
-    trace_reduce<B>(part, red, phase, sum);
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-        u[j] = sum[j] + (f.uniform[j] + x[f.components[j]] * f.bg_scale[j]);
-}
-
-/* This thread's share of one set's vorticity: records tid, tid + B, ... of the
- * velocity functor V's buffer through the gradient functor K (same {r, f}
- * prefix), the partial gradient finished, its curl added to w. */
-template <typename K, typename V, int B>
-__device__ __forceinline__ void trace_add_curl(const double *__restrict__ rec, const long long n,
-                                               const double (&x)[3],
-                                               const typename K::Params &params, double (&w)[3]) {
-    static_assert(K::SRCDIM == V::SRCDIM && K::AUXDIM == 0, "K reads the prefix of V's record");
-    constexpr int STRIDE = rec_doubles<V>();
-    constexpr int R = rec_doubles<K>();
-    double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    unsigned zmin = ~0u;
-    for (long long s = threadIdx.x; s < n; s += B) {
-        const double *__restrict__ p = rec + STRIDE * s;
-        double v[R];
-#pragma unroll
-        for (int i = 0; i < R; ++i)
-            v[i] = p[i];
-        K::template pair<true>(x, v, v + 3, v + 3 + K::SRCDIM, acc, params, zmin);
-    }
-    w[0] += K::finish(acc[7], params) - K::finish(acc[5], params);
-    w[1] += K::finish(acc[2], params) - K::finish(acc[6], params);
-    w[2] += K::finish(acc[3], params) - K::finish(acc[1], params);
-}
-
-/* curl u(x), the same bits in every thread; arguments and calling rule as
- * trace_field. */
-template <int B>
-__device__ __forceinline__ void trace_vorticity(const TraceField &f, const double (&x)[3],
-                                                double (*red)[B / 64][3], int &phase,
-                                                double (&w)[3]) {
-    /* rigid rotation inside a body */
-    const int inside = trace_body_at(f, x);
-    if (inside >= 0) {
-        const double *q = f.bodies + SKELLY_TRACE_BODY_DOUBLES * inside;
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            w[j] = 2.0 * q[7 + j];
-        return;
-    }
-
-    double part[3] = {0.0, 0.0, 0.0};
-    trace_add_curl<StokesletGrad, Stokeslet, B>(f.rec[0], f.n[0], x, f.gsl, part);
-    trace_add_curl<StressletGrad, Stresslet, B>(f.rec[1], f.n[1], x, f.gdl, part);
-    trace_add_curl<RotletGrad, Rotlet, B>(f.rec[2], f.n[2], x, f.grot, part);
-    trace_add_curl<StokesletGrad, OseenContract, B>(f.rec[3], f.n[3], x, f.gos, part);
-
-    double sum[3];
-    trace_reduce<B>(part, red, phase, sum);
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-        w[j] = sum[j] + f.bg_curl[j];
-}
-
-/* The field that instantiation FIELD integrates and records. */
-template <int B, int FIELD>
-__device__ __forceinline__ void trace_rhs(const TraceField &f, const double (&x)[3],
-                                          double (*red)[B / 64][3], int &phase, double (&k)[3]) {
-    if (FIELD == TRACE_VORTICITY)
-        trace_vorticity<B>(f, x, red, phase, k);
-    else
-        trace_field<B>(f, x, red, phase, k);
+    trace_rhs<B, TRACE_VELOCITY>(f, x, red, phase, u);
 }
 
 template <int B, int FIELD>
@@ -400,17 +404,7 @@ __global__ __launch_bounds__(B) void trace_lines_kernel(const TraceField f, cons
 
 namespace skelly {
 
-/* Pack one set into the workspace at `rec` (nothing for an empty set). */
-template <typename K>
-static void trace_pack(const double *r_src, const double *f_src, long long n, double *rec,
-                       hipStream_t stream) {
-    if (n <= 0)
-        return;
-    const long long total = (long long)rec_doubles<K>() * rec_count<K>(n);
-    hipLaunchKernelGGL((pack_sources<K>), dim3((unsigned)((total + BLOCK - 1) / BLOCK)),
-                       dim3(BLOCK), 0, stream, r_src, f_src, rec, n);
-}
-
+/* Doubles of a set's record buffer (none for an empty set, which is not packed). */
 template <typename K>
 static size_t trace_rec_doubles(long long n) {
     return n > 0 ? (size_t)rec_doubles<K>() * rec_count<K>(n) : 0;
@@ -443,48 +437,31 @@ hipError_t launch_trace_streamlines(const TraceRequest &q, hipStream_t stream) {
                            trace_rec_doubles<Rotlet>(q.n[2]),
                            trace_rec_doubles<OseenContract>(q.n[3])};
     const size_t ws_bytes = (len[0] + len[1] + len[2] + len[3] + 1) * sizeof(double);
-    double *workspace = nullptr;
-    bool pooled = false;
-    if (g_persistent_ws.get() != 0) {
-        workspace = persistent_ws(stream, ws_bytes);
-        pooled = workspace != nullptr;
-    }
-    if (!pooled) {
-        hipError_t err = hipMallocAsync((void **)&workspace, ws_bytes, stream);
-        if (err != hipSuccess)
-            return err;
-    }
+    LaunchWorkspace workspace;
+    hipError_t err = workspace.acquire(stream, ws_bytes);
+    if (err != hipSuccess)
+        return err;
 
     TraceField f;
-    double *at = workspace;
+    const PairKernel set[4] = {PairKernel::Stokeslet, PairKernel::Stresslet, PairKernel::Rotlet,
+                               PairKernel::OseenContract};
+    double *at = workspace.get();
     for (int k = 0; k < 4; ++k) {
         f.rec[k] = at;
         f.n[k] = q.n[k];
+        if (q.n[k] > 0)
+            launch_pack_sources(set[k], q.r[k], q.f[k], q.n[k], at, stream);
         at += len[k];
     }
-    trace_pack<Stokeslet>(q.r[0], q.f[0], q.n[0], workspace, stream);
-    trace_pack<Stresslet>(q.r[1], q.f[1], q.n[1], workspace + len[0], stream);
-    trace_pack<Rotlet>(q.r[2], q.f[2], q.n[2], workspace + len[0] + len[1], stream);
-    trace_pack<OseenContract>(q.r[3], q.f[3], q.n[3], workspace + len[0] + len[1] + len[2],
-                              stream);
-    /* the functors accumulate ACC_FOLD x the sum (launch_pair) */
-    f.sl = Stokeslet::make_params(q.scale_stokes, q.reg, q.eps);
-    f.sl.scale /= Stokeslet::ACC_FOLD;
-    f.dl = Stresslet::make_params(q.scale_stokes, q.reg, q.eps);
-    f.dl.scale /= Stresslet::ACC_FOLD;
-    f.rot = Rotlet::make_params(q.scale_oseen, q.reg, q.eps);
-    f.rot.scale /= Rotlet::ACC_FOLD;
-    f.os = OseenContract::make_params(q.scale_oseen, q.reg, q.eps);
-    f.os.scale /= OseenContract::ACC_FOLD;
+    f.sl = launch_params<Stokeslet>(q.scale_stokes, q.reg, q.eps);
+    f.dl = launch_params<Stresslet>(q.scale_stokes, q.reg, q.eps);
+    f.rot = launch_params<Rotlet>(q.scale_oseen, q.reg, q.eps);
+    f.os = launch_params<OseenContract>(q.scale_oseen, q.reg, q.eps);
     /* the vorticity's functors: the prefactors of the gradient entry points */
-    f.gsl = StokesletGrad::make_params(q.scale_stokes, 0.0, 0.0);
-    f.gsl.scale /= StokesletGrad::ACC_FOLD;
-    f.gdl = StressletGrad::make_params(q.scale_stokes, q.reg, q.eps);
-    f.gdl.scale /= StressletGrad::ACC_FOLD;
-    f.grot = RotletGrad::make_params(q.scale_oseen, q.reg, q.eps);
-    f.grot.scale /= RotletGrad::ACC_FOLD;
-    f.gos = StokesletGrad::make_params(q.scale_oseen, q.reg, q.eps);
-    f.gos.scale /= StokesletGrad::ACC_FOLD;
+    f.gsl = launch_params<StokesletGrad>(q.scale_stokes, 0.0, 0.0);
+    f.gdl = launch_params<StressletGrad>(q.scale_stokes, q.reg, q.eps);
+    f.grot = launch_params<RotletGrad>(q.scale_oseen, q.reg, q.eps);
+    f.gos = launch_params<StokesletGrad>(q.scale_oseen, q.reg, q.eps);
     for (int j = 0; j < 3; ++j) {
         f.uniform[j] = q.uniform[j];
         f.bg_scale[j] = q.bg_scale[j];
@@ -509,7 +486,7 @@ hipError_t launch_trace_streamlines(const TraceRequest &q, hipStream_t stream) {
     jobs.status = q.status;
 
     /* a job that never ran shows as count -1 (all bits set) */
-    hipError_t err = hipMemsetAsync(q.count, 0xFF, (size_t)n_jobs * sizeof(int), stream);
+    err = hipMemsetAsync(q.count, 0xFF, (size_t)n_jobs * sizeof(int), stream);
     if (err == hipSuccess) {
         const dim3 grid((unsigned)n_jobs), block(SKELLY_TRACE_BLOCK);
         if (q.vorticity)
@@ -520,10 +497,7 @@ hipError_t launch_trace_streamlines(const TraceRequest &q, hipStream_t stream) {
                                block, 0, stream, f, jobs);
         err = hipGetLastError();
     }
-    if (pooled)
-        return err;
-    hipError_t err2 = hipFreeAsync(workspace, stream);
-    return err != hipSuccess ? err : err2;
+    return workspace.finish(err);
 }
 
 int trace_block_size() { return SKELLY_TRACE_BLOCK; }

@@ -1,9 +1,11 @@
-/* streamline_probe — include/skelly_evaluator.hpp's trace_streamlines called
- * from C++: reads a case written by tests/test_gpu_streamlines.py and prints
- * one joined line, a row "t x y z vx vy vz" per point with 17 digits, so that
- * the test can compare it with the Python result bit for bit.
+/* fieldline_probe — include/skelly_evaluator.hpp's trace_streamlines or
+ * trace_vortexlines called from C++: reads a case written by
+ * tests/test_gpu_streamlines.py or tests/test_gpu_vortexlines.py and prints one
+ * joined line, a row "t x y z vx vy vz" per point (val is u for a streamline,
+ * curl u for a vortex line) with 17 digits, so that the test can compare it
+ * with the Python result bit for bit.
  *
- *   streamline_probe case.bin seed_index
+ *   fieldline_probe streamlines|vortexlines case.bin seed_index
  *
  * case.bin: int64 {n_sl, n_dl, n_rot, n_os, n_bodies, n_seeds, back_integrate,
  * max_points, has_background}, doubles {eta, reg, eps, dt_init, t_final,
@@ -15,6 +17,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 static std::vector<double> read_doubles(std::FILE *f, long n) {
@@ -27,13 +30,14 @@ static std::vector<double> read_doubles(std::FILE *f, long n) {
 }
 
 int main(int argc, char **argv) {
-    if (argc != 3) {
-        std::fprintf(stderr, "usage: %s case.bin seed_index\n", argv[0]);
+    const bool vortex = argc == 4 && !std::strcmp(argv[1], "vortexlines");
+    if (argc != 4 || (!vortex && std::strcmp(argv[1], "streamlines"))) {
+        std::fprintf(stderr, "usage: %s streamlines|vortexlines case.bin seed_index\n", argv[0]);
         return 2;
     }
-    std::FILE *f = std::fopen(argv[1], "rb");
+    std::FILE *f = std::fopen(argv[2], "rb");
     if (!f) {
-        std::perror(argv[1]);
+        std::perror(argv[2]);
         return 2;
     }
     long long h[9];
@@ -71,16 +75,17 @@ int main(int argc, char **argv) {
     field.epsilon_distance = s[2];
 
     try {
-        const std::vector<skelly::StreamLine> lines = skelly::trace_streamlines(
+        const auto trace = vortex ? skelly::trace_vortexlines : skelly::trace_streamlines;
+        const std::vector<skelly::StreamLine> lines = trace(
             field, {seeds.data(), 3, (long)h[5]}, s[3], s[4], s[5], s[6], h[6] != 0, (long)h[7]);
-        const skelly::StreamLine &line = lines.at(std::atol(argv[2]));
+        const skelly::StreamLine &line = lines.at(std::atol(argv[3]));
         std::printf("lines %zu status %d points %ld\n", lines.size(), line.status, line.x.cols());
         for (long c = 0; c < line.x.cols(); ++c)
             std::printf("%.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", line.time[c], line.x(0, c),
                         line.x(1, c), line.x(2, c), line.val(0, c), line.val(1, c),
                         line.val(2, c));
     } catch (const std::exception &e) {
-        std::fprintf(stderr, "trace_streamlines threw: %s\n", e.what());
+        std::fprintf(stderr, "trace_%s threw: %s\n", argv[1], e.what());
         return 1;
     }
     return 0;

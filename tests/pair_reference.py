@@ -1,9 +1,9 @@
 """Extended-precision references of the pair kernels, with the condition sum
 and the rounding bound that judge a kernel per target and per component.
 
-Every functor of skellysim_amd/csrc/pair_kernels.hip and the two dense
-builders are restated here from their formulas in np.longdouble (64-bit
-mantissa), vectorised over (targets, sources). Each function returns
+Every functor of skellysim_amd/csrc/pair_functors.hpp and the two dense
+builders of pair_kernels.hip are restated here from their formulas in
+np.longdouble (64-bit mantissa), vectorised over (targets, sources). Each function returns
 (ref, A): `ref` is the value, `A` has its shape and is the same expression
 with every product replaced by its absolute value and every sum by a sum of
 absolute values, prefactor included: the condition sum. |out - ref| is judged

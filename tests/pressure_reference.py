@@ -1,5 +1,5 @@
 """Extended-precision references of the pressure functors (StokesletPressure,
-StressletPressure of skellysim_amd/csrc/pair_kernels.hip), in the manner of
+StressletPressure of skellysim_amd/csrc/pair_functors.hpp), in the manner of
 tests/pair_reference.py and with its conventions: np.longdouble, d = t - s,
 y = 1/sqrt(den), the r == 0 mask, (ref, A) with A the condition sum (every
 product replaced by its absolute value, every sum by a sum of absolute values,

@@ -1,4 +1,5 @@
-"""The pair kernels' unmasked fast path (csrc/pair_kernels.hip): each chunk of
+"""The pair kernels' unmasked fast path (pair_driver of csrc/pair_kernels.hip over
+the pair<false> of the functors of csrc/pair_functors.hpp): each chunk of
 sources runs without the r == 0 mask and is rerun masked only when a lane's
 accumulator went NaN (oseen: when a tracked r^2 hit zero). Every case is
 checked two ways: against the CPU oracle at the parity bar of

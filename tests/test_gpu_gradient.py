@@ -1,4 +1,4 @@
-"""GPU tests of the analytic velocity-gradient kernels (csrc/pair_kernels.hip:
+"""GPU tests of the analytic velocity-gradient kernels (csrc/pair_functors.hpp:
 StokesletGrad, StressletGrad, RotletGrad through the shared pair driver).
 
 Expected values are the numpy closed forms of tests/test_gradient_cpu.py,

@@ -1,4 +1,4 @@
-"""GPU tests of the pressure kernels (csrc/pair_kernels.hip: StokesletPressure,
+"""GPU tests of the pressure kernels (csrc/pair_functors.hpp: StokesletPressure,
 which is also the regularized Oseen pressure, and StressletPressure, through
 the shared pair driver) and of the stress layers on top of them.
 

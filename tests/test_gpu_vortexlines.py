@@ -401,8 +401,8 @@ class _VortexWithSets(_WithSets):
 
 
 def test_cpp_mirror_prints_the_python_line(backend, tmp_path):
-    """tests/vortexline_probe.cpp through include/skelly_evaluator.hpp (the
-    host form) against flows.vortexlines_at_seeds (the device form), all four
+    """tests/fieldline_probe.cpp (vortexlines) through include/skelly_evaluator.hpp
+    (the host form) against flows.vortexlines_at_seeds (the device form), all four
     sets, the background and a body: the same joined line, bit for bit."""
     from skellysim_amd.flows import vortexlines_at_seeds
     c = S.mixed_cloud()
@@ -410,11 +410,11 @@ def test_cpp_mirror_prints_the_python_line(backend, tmp_path):
     cxx = next((x for x in (os.environ.get("CXX"), "g++", "c++", "clang++")
                 if x and shutil.which(x)), None)
     assert cxx, "no host C++ compiler"
-    exe, case = str(tmp_path / "vortexline_probe"), str(tmp_path / "case.bin")
+    exe, case = str(tmp_path / "fieldline_probe"), str(tmp_path / "case.bin")
     libdir = os.path.join(REPO, "skellysim_amd")
     built = subprocess.run(
         [cxx, "-O2", "-std=c++17", "-I", os.path.join(REPO, "include"),
-         os.path.join(REPO, "tests", "vortexline_probe.cpp"), "-L", libdir, "-lskellyhip",
+         os.path.join(REPO, "tests", "fieldline_probe.cpp"), "-L", libdir, "-lskellyhip",
          "-Wl,-rpath," + libdir, "-o", exe], capture_output=True, text=True)
     assert built.returncode == 0, built.stderr
     order = ("stokeslet", "stresslet", "rotlet", "oseen")
@@ -430,8 +430,9 @@ def test_cpp_mirror_prints_the_python_line(backend, tmp_path):
         body.tofile(f)
         np.ascontiguousarray(c["seeds"]).tofile(f)
     seed = 3
-    r = subprocess.run([exe, case, str(seed)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, f"vortexline_probe failed ({r.returncode}): {r.stdout} {r.stderr}"
+    r = subprocess.run([exe, "vortexlines", case, str(seed)], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, f"fieldline_probe failed ({r.returncode}): {r.stdout} {r.stderr}"
     head, *rows = r.stdout.strip().splitlines()
     got = np.array([[float(v) for v in row.split()] for row in rows])
 
