@@ -194,6 +194,37 @@ inline MatrixXd oseen_tensor_contract_pressure(const CMatrixRef &r_src, const CM
     return p;
 }
 
+/* Nearest source (no reference counterpart; skelly_nearest_host): per column
+ * of r_trg the squared distance to the nearest eligible column of r_src and
+ * that column's index, the lowest among equals; +inf and -1 where there is
+ * none. With groups (both vectors non-empty, one id per column) a source is
+ * eligible when its id differs from the target's; with both empty every
+ * source is. */
+struct Nearest {
+    std::vector<double> d2;
+    std::vector<long long> index;
+};
+
+inline Nearest nearest(const CMatrixRef &r_src, const CMatrixRef &r_trg,
+                       const std::vector<long long> &src_group = {},
+                       const std::vector<long long> &trg_group = {}) {
+    const long n_src = r_src.size() / 3, n_trg = r_trg.size() / 3;
+    const bool grouped = !src_group.empty() || !trg_group.empty();
+    if (grouped && ((long)src_group.size() != n_src || (long)trg_group.size() != n_trg))
+        throw std::runtime_error("nearest: one group id per source and per target, or none");
+    Nearest out;
+    out.d2.resize(n_trg);
+    out.index.resize(n_trg);
+    /* an empty vector's data() may be null: a grouped call never passes it */
+    static const long long none = 0;
+    check_rc(skelly_nearest_host(r_src.ptr, grouped ? (n_src ? src_group.data() : &none) : nullptr,
+                                 n_src, r_trg.ptr,
+                                 grouped ? (n_trg ? trg_group.data() : &none) : nullptr, n_trg,
+                                 out.d2.data(), out.index.data()),
+             "nearest");
+    return out;
+}
+
 /* Streamlines (mirror of StreamLine::compute, streamline.cpp:67-113, for all
  * seeds in one kernel launch; skelly_trace_streamlines_host). The field is the
  * sum of the four source sets of StreamlineField, each possibly empty, plus

@@ -220,6 +220,35 @@ int skelly_oseen_contract_pressure_device(const double *d_r_src, const double *d
                                           long long n_src, long long n_trg,
                                           double reg, double epsilon_distance, void *stream);
 
+/* ---- nearest source ----
+ *
+ * For every target the nearest eligible source: d2[t] = min |r_trg[t] -
+ * r_src[s]|^2 (squared, no root is taken) and index[t] the s that attains it.
+ * A source is eligible when its group id differs from the target's; with both
+ * group pointers NULL every source is eligible. Exactly one NULL group pointer
+ * is an error, found like a negative count before any HIP call
+ * ("<entry point>: one group array without the other").
+ *   Ties     among equal d2 the lowest source index wins.
+ *   Nothing  no eligible source (n_src == 0, every source in the target's
+ *            group, a target with a NaN coordinate): d2 = +inf, index = -1.
+ *   NaN      a source with a NaN coordinate is never returned.
+ *   Zero     a coincident eligible source is a hit with d2 == 0.
+ * d2 is computed as fma(dz, dz, fma(dy, dy, dx * dx)), d = r_trg - r_src.
+ * Results are bit-identical for every source-slice count
+ * (skelly_set_pair_slices) and from run to run: a minimum has no summation
+ * order. d_d2 is double[n_trg], d_index long long[n_trg], both overwritten.
+ * The device form is asynchronous on `stream`, performs no synchronization and
+ * takes all its scratch (packed records, partials, the converted group ids)
+ * from the stream's persistent workspace, so after one warm-up call it
+ * allocates nothing and can be captured. n_trg == 0 returns 0 and touches
+ * nothing. */
+int skelly_nearest_device(const double *d_r_src, const long long *d_src_group, long long n_src,
+                          const double *d_r_trg, const long long *d_trg_group, long long n_trg,
+                          double *d_d2, long long *d_index, void *stream);
+int skelly_nearest_host(const double *r_src, const long long *src_group, long long n_src,
+                        const double *r_trg, const long long *trg_group, long long n_trg,
+                        double *d2, long long *index);
+
 /* Contraction of the stresslet with a normal and a density field over one
  * point set (kernels::stresslet_times_normal_times_density,
  * src/core/kernels.cpp:307-334; no eta dependence, factor -3/(4*pi)):

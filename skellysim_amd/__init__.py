@@ -43,6 +43,8 @@ from .evaluator import (  # noqa: F401
     trace_streamlines_device,
     trace_vortexlines_device,
     join_streamlines,
+    nearest,
+    nearest_device,
 )
 from .sharded import ShardedPairEvaluator, shard_sizes, allgather_rows  # noqa: F401
 

@@ -81,6 +81,17 @@ def _trace_args(p, ip):
             + [p, p, p, ip, ip])                # x, t, val, count, status
 
 
+class NearestCount(ctypes.c_longlong):
+    """The `long long` counts of the nearest-source entry points: a type of its
+    own for the reason PressureCount is one (tests/test_nearest_cpu.py checks
+    these entry points' argument contract)."""
+
+
+def _nearest_args(p):
+    """skelly_nearest_*: (r_src, src_group, n_src, r_trg, trg_group, n_trg, d2, index)."""
+    return [p, p, NearestCount, p, p, NearestCount, p, p]
+
+
 def strength_first(symbol):
     """Whether skelly_<symbol>_* take (r_src, f_src, n_src, r_trg, ...), the
     strength orders, and not (r_src, r_trg, density, ...)."""
@@ -113,6 +124,8 @@ SIGNATURES = {
     "skelly_trace_vortexlines_host": (_I, _trace_args(_DP, ctypes.POINTER(_I))),
     "skelly_trace_vortexlines_device": (_I, _trace_args(_PV, _PV) + [_PV]),
     "skelly_trace_block_size": (_I, []),
+    "skelly_nearest_host": (_I, _nearest_args(_PV)),
+    "skelly_nearest_device": (_I, _nearest_args(_PV) + [_PV]),
 }
 for _name, _family in PAIR_FAMILY.items():
     SIGNATURES[f"skelly_{_name}_host"] = (_I, _PAIR_ARGS[_family](_DP))

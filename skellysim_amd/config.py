@@ -45,6 +45,16 @@ def build_fibers(cfg, eta):
     return fibers
 
 
+def _generic_contact(cfg):
+    """Whether the config opts into contact against a periphery of any other
+    shape than sphere or ellipsoid, through its nodes and normals
+    (contact.py): [params] generic_periphery_contact = true, an ENGINE
+    EXTENSION key no reference config has. Without it such a periphery has no
+    collision test and no steric force, as in the reference."""
+    return "periphery" in cfg and \
+        bool(cfg.get("params", {}).get("generic_periphery_contact", False))
+
+
 def periphery_shape_from(cfg):
     """dict(kind, radius|abc) for collision/binding geometry."""
     per = cfg.get("periphery", {})
@@ -52,6 +62,9 @@ def periphery_shape_from(cfg):
         return dict(kind="sphere", radius=per["radius"])
     if per.get("shape") == "ellipsoid":
         return dict(kind="ellipsoid", abc=(per["a"], per["b"], per["c"]))
+    if _generic_contact(cfg):
+        # nodes and normals: build_system's, from the shell geometry
+        return dict(kind="generic")
     return None
 
 
@@ -68,6 +81,8 @@ def periphery_interaction_from(cfg):
         return dict(kind="sphere", radius=per["radius"], **kw)
     if per.get("shape") == "ellipsoid":
         return dict(kind="ellipsoid", abc=(per["a"], per["b"], per["c"]), **kw)
+    if _generic_contact(cfg):
+        return dict(kind="generic", **kw)
     return None
 
 
@@ -202,11 +217,16 @@ def build_system(cfg, backend=None, shell_geometry=None, dt=None,
     di = params.get("dynamic_instability")
     if di is not None and di.get("n_nodes", 0) == 0:
         di = None
+    interaction, shape = periphery_interaction_from(cfg), periphery_shape_from(cfg)
+    for spec in (interaction, shape):
+        # generic-periphery contact works on the shell geometry's own nodes
+        if spec is not None and spec["kind"] == "generic" and shell is not None:
+            spec.update(nodes=shell.nodes, normals=shell.normals)
     system = SystemFD(fibers, eta=eta, dt=dt, shell=shell,
                       background_flow=background_flow, backend=backend,
-                      periphery_interaction=periphery_interaction_from(cfg),
+                      periphery_interaction=interaction,
                       bodies=bodies,
-                      periphery_shape=periphery_shape_from(cfg),
+                      periphery_shape=shape,
                       periphery_binding=params.get("periphery_binding"),
                       dynamic_instability=di,
                       seed=params.get("seed", 130319))

@@ -1,5 +1,5 @@
 /* pair_functors.hpp — the per-pair arithmetic of every kernel unit: the fp64
- * rsqrt, the ten pair functors and the layout of a packed source record.
+ * rsqrt, the eleven pair functors (ten sums and one arg-min) and the layout of a packed source record.
  * Device code, but for launch_params() at the end. pair_kernels.hip
  * (pair_driver, the dense builders), trace_kernels.hip (the field-line tracer)
  * and probe_kernels.hip (the rsq probe) include it, so that all three run the
@@ -71,11 +71,21 @@ __device__ inline double rsq_refined(double x) { return 0.5 * rsq_x2(x); }
  *   MAX_TPT    most targets a thread holds (register budget).
  *   GROUP      sources per group of scalar record loads (SGPR budget: two
  *              groups of GROUP x 2 x (3 + SRCDIM + AUXDIM) SGPRs are live).
- *   FASTPATH   the unmasked chunk-rerun path is wired (needs HAS_MASK). */
+ *   FASTPATH   the unmasked chunk-rerun path is wired (needs HAS_MASK).
+ *   TRGDIM     doubles per target: the coordinates, then what the functor
+ *              reads beside them (Nearest: the target's group id).
+ *   init(j)    what accumulator j starts from: the neutral element of the
+ *              functor's reduction, which an empty slice writes.
+ *   JOINT      a target's OUTDIM partials of two slices combine as one value
+ *              (combine(), in slice order) instead of component by component. */
 
-/* What every functor finishes with: the prefactor, applied once (linear in
- * the sum). P is the functor's Params. */
+/* What every functor has unless it says otherwise: a sum from zero over
+ * three target coordinates, finished with the prefactor, applied once (linear
+ * in the sum). P is the functor's Params. */
 struct PairFunctor {
+    static constexpr int TRGDIM = 3;
+    static constexpr bool JOINT = false;
+    __device__ static inline double init(int) { return 0.0; }
     template <typename P>
     __device__ static inline double finish(double a, const P &p) {
         return a * p.scale;
@@ -581,6 +591,67 @@ struct StressletPressure : PressureTraits, ScaleParams { /* scale: 1/(4*pi) */
         const double tr = (f[0] + f[4]) + f[8];
         const double q = __builtin_fma(-0.75 * R2, C, tr);
         acc[0] = __builtin_fma(R3, q, acc[0]);
+    }
+};
+
+/* ---- nearest source ------------------------------------------------------
+ * Not a sum but an arg-min: per target the smallest d^2 = |t - s|^2 over the
+ * eligible sources and the index of the source that attains it, in
+ * acc = {d^2, index}. The record is {r[3], index, group} and the target
+ * carries its group id as a fourth double (ids and indices as exact doubles);
+ * a source is eligible when its group differs from the target's. Ungrouped
+ * calls give every source group 0 and every target group -1.
+ *   - The update is one compare on d^2, one on the group, and selects: no
+ *     rsqrt, no branch. A strict `<` in source order keeps the lowest index
+ *     among equal d^2; combine() does the same across slices in slice order,
+ *     so the result is the same for every slice count and target-per-thread
+ *     count, bit for bit.
+ *   - acc starts from {+inf, -1}: that is the answer for no eligible source,
+ *     and for a NaN target or source, whose compare is false.
+ *   - Every pair takes the same path (HAS_MASK and FASTPATH off): a
+ *     coincident eligible pair is a hit with d^2 = 0.
+ * GROUP: a record is 5 doubles = 10 SGPRs, two groups in flight. 4 sources a
+ * group (80 SGPRs of records) leaves too few for addresses and counters;
+ * 2 (40) compiles without spills. MAX_TPT 4, MIN_WAVES 4 as the pressures:
+ * 12 VGPRs a target. */
+#ifndef SKELLY_NEAREST_GROUP
+#define SKELLY_NEAREST_GROUP 2
+#endif
+
+struct Nearest : PairFunctor, ScaleParams {
+    static constexpr int OUTDIM = 2;
+    static constexpr int MAX_TPT = 4;
+    static constexpr int MIN_WAVES = 4;
+    static constexpr int GROUP = SKELLY_NEAREST_GROUP;
+    static constexpr int SRCDIM = 2; /* index, group */
+    static constexpr int AUXDIM = 0;
+    static constexpr int TRGDIM = 4; /* r[3], group */
+    static constexpr bool HAS_MASK = false;
+    static constexpr bool FASTPATH = false;
+    static constexpr bool NAN_PROBE = false;
+    static constexpr bool JOINT = true;
+    static constexpr double ACC_FOLD = 1.0;
+    __device__ static inline double init(int j) { return j == 0 ? __builtin_inf() : -1.0; }
+    __device__ static inline double finish(double a, const Params &) { return a; }
+    template <bool MASKED>
+    __device__ static inline void pair(const double t[4], const double sp[3], const double f[2],
+                                       const double *, double acc[2], const Params &,
+                                       unsigned &) {
+        const double dx = t[0] - sp[0];
+        const double dy = t[1] - sp[1];
+        const double dz = t[2] - sp[2];
+        double d2 = dx * dx;
+        d2 = __builtin_fma(dy, dy, d2);
+        d2 = __builtin_fma(dz, dz, d2);
+        const bool better = (d2 < acc[0]) & (f[1] != t[3]);
+        acc[0] = better ? d2 : acc[0];
+        acc[1] = better ? f[0] : acc[1];
+    }
+    /* a <- the better of a and the later slice's b */
+    __device__ static inline void combine(double a[2], const double b[2]) {
+        const bool better = b[0] < a[0];
+        a[0] = better ? b[0] : a[0];
+        a[1] = better ? b[1] : a[1];
     }
 };
 

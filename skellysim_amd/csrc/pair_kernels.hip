@@ -64,6 +64,13 @@
  *   - The same driver evaluates the analytic velocity gradients of the four
  *     kernels (9 outputs a target, K::OUTDIM; functors further down) and
  *     the pressures of the Stokeslet, Oseen and stresslet fields (1 output).
+ *   - One functor is no sum: Nearest keeps per target the smallest squared
+ *     distance to an eligible source and that source's index. The driver
+ *     serves it through three functor traits that default to what the sums
+ *     need: the accumulators start from K::init (the reduction's neutral
+ *     element, which an empty slice of a forced split writes), a target may
+ *     carry more than its coordinates (K::TRGDIM), and reduce_partials folds
+ *     a K::JOINT functor's partials a target at a time with K::combine.
  *
  * Roofline: compute-bound on the fp64 VALU. The kernels are
  * deliberately not GEMM-shaped: gfx950's fp64 matrix rate equals its vector
@@ -141,7 +148,7 @@ __device__ __forceinline__ void load_group(double (&dst)[N], const double *__res
  * this thread's TPT targets, in source order. */
 template <typename K, int TPT, bool MASKED, bool FULL>
 __device__ __forceinline__ void pair_group(const double (&g)[K::GROUP * rec_doubles<K>()],
-                                           const int count, const double (&tp)[TPT][3],
+                                           const int count, const double (&tp)[TPT][K::TRGDIM],
                                            double (&acc)[TPT][K::OUTDIM],
                                            const typename K::Params &params, unsigned &zmin) {
     constexpr int R = rec_doubles<K>();
@@ -169,7 +176,7 @@ __device__ __forceinline__ void pair_group(const double (&g)[K::GROUP * rec_doub
 template <typename K, int TPT, bool MASKED>
 __device__ __forceinline__ void pair_span(const double *__restrict__ rec, const int n,
                                           double (&a)[K::GROUP * rec_doubles<K>()],
-                                          const double (&tp)[TPT][3],
+                                          const double (&tp)[TPT][K::TRGDIM],
                                           double (&acc)[TPT][K::OUTDIM],
                                           const typename K::Params &params, unsigned &zmin) {
     constexpr int G = K::GROUP;
@@ -210,19 +217,22 @@ __global__ __launch_bounds__(BLOCK, K::MIN_WAVES) void pair_driver(const double 
     const int tid = threadIdx.x;
     const long long base = (long long)blockIdx.x * (BLOCK * TPT);
 
-    double tp[TPT][3];
+    constexpr int TD = K::TRGDIM;
+    double tp[TPT][TD];
     constexpr int OD = K::OUTDIM;
     double acc[TPT][OD];
 #pragma unroll
     for (int k = 0; k < TPT; ++k) {
         long long it = base + (long long)k * BLOCK + tid;
         const long long itc = it < n_trg ? it : (n_trg > 0 ? n_trg - 1 : 0);
-        tp[k][0] = r_trg[3 * itc + 0];
-        tp[k][1] = r_trg[3 * itc + 1];
-        tp[k][2] = r_trg[3 * itc + 2];
+        tp[k][0] = r_trg[TD * itc + 0];
+        tp[k][1] = r_trg[TD * itc + 1];
+        tp[k][2] = r_trg[TD * itc + 2];
+        if constexpr (TD > 3)
+            tp[k][3] = r_trg[TD * itc + 3];
 #pragma unroll
         for (int j = 0; j < OD; ++j)
-            acc[k][j] = 0.0;
+            acc[k][j] = K::init(j);
     }
 
     /* An empty use of the target coordinates: the wait for their loads falls
@@ -230,6 +240,11 @@ __global__ __launch_bounds__(BLOCK, K::MIN_WAVES) void pair_driver(const double 
 #pragma unroll
     for (int k = 0; k < TPT; ++k)
         asm volatile("" : "+v"(tp[k][0]), "+v"(tp[k][1]), "+v"(tp[k][2]));
+    if constexpr (TD > 3) {
+#pragma unroll
+        for (int k = 0; k < TPT; ++k)
+            asm volatile("" : "+v"(tp[k][3]));
+    }
 
     /* slice_len = ceil(n_src / gridDim.y) comes from the host: a 64-bit
      * division here would leave the slice start, and every record address
@@ -314,7 +329,9 @@ __global__ __launch_bounds__(BLOCK, K::MIN_WAVES) void pair_driver(const double 
 }
 
 /* Sum source-slice partials in fixed slice order and apply the finish scale.
- * partial layout: [n_slices][n_trg][OUTDIM]; one thread per (target, component). */
+ * partial layout: [n_slices][n_trg][OUTDIM]; one thread per (target, component).
+ * A K::JOINT functor's partials are one value a target: one thread per target
+ * folds them with K::combine from K::init, in slice order. */
 template <typename K>
 __global__ __launch_bounds__(BLOCK) void reduce_partials(const double *__restrict__ partial,
                                                          double *__restrict__ u_trg,
@@ -322,12 +339,65 @@ __global__ __launch_bounds__(BLOCK) void reduce_partials(const double *__restric
                                                          typename K::Params params) {
     const long long n_out = K::OUTDIM * n_trg;
     const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n_out)
+    if constexpr (K::JOINT) {
+        constexpr int OD = K::OUTDIM;
+        if (i >= n_trg)
+            return;
+        double a[OD], b[OD];
+#pragma unroll
+        for (int j = 0; j < OD; ++j)
+            a[j] = K::init(j);
+        for (int y = 0; y < n_slices; ++y) {
+#pragma unroll
+            for (int j = 0; j < OD; ++j)
+                b[j] = partial[(long long)y * n_out + OD * i + j];
+            K::combine(a, b);
+        }
+#pragma unroll
+        for (int j = 0; j < OD; ++j)
+            u_trg[OD * i + j] = K::finish(a[j], params);
+    } else {
+        if (i >= n_out)
+            return;
+        double s = 0.0;
+        for (int y = 0; y < n_slices; ++y)
+            s += partial[(long long)y * n_out + i];
+        u_trg[i] = K::finish(s, params);
+    }
+}
+
+/* skelly_nearest_*'s arguments as the Nearest functor reads them: one thread
+ * per index writes source i's strength {i, group} and target i's four doubles
+ * {r[3], group}. Without groups (both pointers null) every source is in group
+ * 0 and every target in group -1. */
+__global__ __launch_bounds__(BLOCK) void stage_nearest(const long long *__restrict__ src_group,
+                                                       long long n_src,
+                                                       const double *__restrict__ r_trg,
+                                                       const long long *__restrict__ trg_group,
+                                                       long long n_trg, double *__restrict__ f_src,
+                                                       double *__restrict__ trg4) {
+    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n_src) {
+        f_src[2 * i + 0] = (double)i;
+        f_src[2 * i + 1] = src_group ? (double)src_group[i] : 0.0;
+    }
+    if (i < n_trg) {
+        trg4[4 * i + 0] = r_trg[3 * i + 0];
+        trg4[4 * i + 1] = r_trg[3 * i + 1];
+        trg4[4 * i + 2] = r_trg[3 * i + 2];
+        trg4[4 * i + 3] = trg_group ? (double)trg_group[i] : -1.0;
+    }
+}
+
+/* The functor's {d^2, index} pairs into the caller's two arrays. */
+__global__ __launch_bounds__(BLOCK) void unpack_nearest(const double *__restrict__ out2,
+                                                        long long n_trg, double *__restrict__ d2,
+                                                        long long *__restrict__ index) {
+    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n_trg)
         return;
-    double s = 0.0;
-    for (int y = 0; y < n_slices; ++y)
-        s += partial[(long long)y * n_out + i];
-    u_trg[i] = K::finish(s, params);
+    d2[i] = out2[2 * i + 0];
+    index[i] = (long long)out2[2 * i + 1];
 }
 
 /* ---- launch helpers (host) -------------------------------------------- */
@@ -413,15 +483,25 @@ static void launch_pack(const double *r_src, const double *f_src, long long n_sr
                        dim3(BLOCK), 0, stream, r_src, f_src, rec, n_src);
 }
 
-/* `params` as launch_params<K> made them. */
+/* What a launch of n_trg >= 1 targets is made of: targets a thread, target
+ * blocks, source slices, the fast-path switch, and the doubles of workspace
+ * it takes (the packed source records, then, for split launches, the
+ * partials of every slice). */
+struct PairLaunch {
+    int tpt;
+    long long blocks;
+    int n_slices;
+    int fast;
+    size_t rec_doubles_total;
+    size_t partial_doubles;
+    size_t doubles() const { return rec_doubles_total + partial_doubles; }
+};
+
 template <typename K>
-static hipError_t launch_pair(const double *r_src, const double *f_src, const double *r_trg,
-                              double *u_trg, long long n_src, long long n_trg,
-                              typename K::Params params, hipStream_t stream) {
-    if (n_trg <= 0)
-        return hipSuccess;
-    const int tpt = pick_tpt<K>(n_trg);
-    const long long blocks = (n_trg + (long long)BLOCK * tpt - 1) / ((long long)BLOCK * tpt);
+static PairLaunch plan_launch(long long n_src, long long n_trg) {
+    PairLaunch l;
+    l.tpt = pick_tpt<K>(n_trg);
+    l.blocks = (n_trg + (long long)BLOCK * l.tpt - 1) / ((long long)BLOCK * l.tpt);
 
     /* Source slices from the CU load-balance model (pair_plan.hpp): the
      * slice count that leaves the CUs the least uneven numbers of
@@ -432,20 +512,25 @@ static hipError_t launch_pair(const double *r_src, const double *f_src, const do
     const PairPlan plan =
         pair_plan(n_src, n_trg, K::MAX_TPT, K::OUTDIM, g_pair_fastpath.get(),
                   PAIR_FASTPATH_MIN_SRC, pair_device_cus(), K::MIN_WAVES, g_pair_slices.get());
-    const int n_slices = plan.n_slices;
-    const int fast = plan.fast;
+    l.n_slices = plan.n_slices;
+    l.fast = plan.fast;
+    l.rec_doubles_total = (size_t)rec_doubles<K>() * rec_count<K>(n_src);
+    l.partial_doubles = l.n_slices > 1 ? (size_t)l.n_slices * K::OUTDIM * n_trg : 0;
+    return l;
+}
 
-    /* Workspace: the packed source records, then (split launches) the
-     * partials of every slice. */
-    const size_t rec_doubles_total = (size_t)rec_doubles<K>() * rec_count<K>(n_src);
-    const size_t partial_doubles = n_slices > 1 ? (size_t)n_slices * K::OUTDIM * n_trg : 0;
-    const size_t ws_bytes = (rec_doubles_total + partial_doubles) * sizeof(double);
-    LaunchWorkspace workspace;
-    const hipError_t err = workspace.acquire(stream, ws_bytes);
-    if (err != hipSuccess)
-        return err;
-    double *rec = workspace.get();
-    double *partials = rec + rec_doubles_total;
+/* The kernels of launch `l` onto `stream`, working in the l.doubles() doubles
+ * at `ws`. r_trg is (n_trg, K::TRGDIM); `params` as launch_params<K> made
+ * them. */
+template <typename K>
+static void enqueue_pair(const PairLaunch &l, double *ws, const double *r_src,
+                         const double *f_src, const double *r_trg, double *u_trg,
+                         long long n_src, long long n_trg, typename K::Params params,
+                         hipStream_t stream) {
+    const int tpt = l.tpt, n_slices = l.n_slices, fast = l.fast;
+    const long long blocks = l.blocks;
+    double *rec = ws;
+    double *partials = rec + l.rec_doubles_total;
 
     const long long slice_len = (n_src + n_slices - 1) / n_slices;
     dim3 block(BLOCK);
@@ -463,10 +548,25 @@ static hipError_t launch_pair(const double *r_src, const double *f_src, const do
     } else {
         /* split path: same TPT, gridDim.y source slices into the partials */
         launch_driver(std::true_type{}, dim3((unsigned)blocks, (unsigned)n_slices), partials);
-        const long long rblocks = (K::OUTDIM * n_trg + BLOCK - 1) / BLOCK;
+        const long long rthreads = K::JOINT ? n_trg : K::OUTDIM * n_trg;
+        const long long rblocks = (rthreads + BLOCK - 1) / BLOCK;
         hipLaunchKernelGGL((reduce_partials<K>), dim3((unsigned)rblocks), block, 0, stream,
                            partials, u_trg, n_trg, n_slices, params);
     }
+}
+
+template <typename K>
+static hipError_t launch_pair(const double *r_src, const double *f_src, const double *r_trg,
+                              double *u_trg, long long n_src, long long n_trg,
+                              typename K::Params params, hipStream_t stream) {
+    if (n_trg <= 0)
+        return hipSuccess;
+    const PairLaunch l = plan_launch<K>(n_src, n_trg);
+    LaunchWorkspace workspace;
+    const hipError_t err = workspace.acquire(stream, l.doubles() * sizeof(double));
+    if (err != hipSuccess)
+        return err;
+    enqueue_pair<K>(l, workspace.get(), r_src, f_src, r_trg, u_trg, n_src, n_trg, params, stream);
     return workspace.finish(hipGetLastError());
 }
 
@@ -494,6 +594,8 @@ static auto with_kernel(PairKernel kernel, F &&f) {
         return f(StokesletPressure{});
     case PairKernel::StressletPressure:
         return f(StressletPressure{});
+    case PairKernel::Nearest:
+        return f(Nearest{});
     }
     __builtin_unreachable();
 }
@@ -513,6 +615,38 @@ hipError_t launch_pair_kernel(PairKernel kernel, const double *r_src, const doub
         return launch_pair<K>(r_src, f_src, r_trg, out, n_src, n_trg,
                               launch_params<K>(scale, reg, eps), stream);
     });
+}
+
+/* The Nearest functor on the entry points' own types. One workspace block
+ * holds the launch's records and partials, then the staged strengths
+ * (n_src, 2), the 4-wide targets and the functor's (n_trg, 2) result, which
+ * unpack_nearest splits into d2 and index. */
+hipError_t launch_nearest(const double *r_src, const long long *src_group, long long n_src,
+                          const double *r_trg, const long long *trg_group, long long n_trg,
+                          double *d2, long long *index, hipStream_t stream) {
+    if (n_trg <= 0)
+        return hipSuccess;
+    using K = Nearest;
+    const PairLaunch l = plan_launch<K>(n_src, n_trg);
+    const size_t f_doubles = (size_t)K::SRCDIM * n_src, trg_doubles = (size_t)K::TRGDIM * n_trg;
+    const size_t out_doubles = (size_t)K::OUTDIM * n_trg;
+    LaunchWorkspace workspace;
+    const hipError_t err = workspace.acquire(
+        stream, (l.doubles() + f_doubles + trg_doubles + out_doubles) * sizeof(double));
+    if (err != hipSuccess)
+        return err;
+    double *f_src = workspace.get() + l.doubles();
+    double *trg4 = f_src + f_doubles;
+    double *out2 = trg4 + trg_doubles;
+    const long long n_max = n_src > n_trg ? n_src : n_trg;
+    const dim3 grid((unsigned)((n_max + BLOCK - 1) / BLOCK)), block(BLOCK);
+    hipLaunchKernelGGL(stage_nearest, grid, block, 0, stream, src_group, n_src, r_trg, trg_group,
+                       n_trg, f_src, trg4);
+    enqueue_pair<K>(l, workspace.get(), r_src, f_src, trg4, out2, n_src, n_trg,
+                    launch_params<K>(1.0, 0.0, 0.0), stream);
+    hipLaunchKernelGGL(unpack_nearest, dim3((unsigned)((n_trg + BLOCK - 1) / BLOCK)), block, 0,
+                       stream, out2, n_trg, d2, index);
+    return workspace.finish(hipGetLastError());
 }
 
 void launch_pack_sources(PairKernel kernel, const double *r_src, const double *f_src,

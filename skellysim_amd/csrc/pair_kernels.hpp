@@ -22,6 +22,7 @@ enum class PairKernel {
     RotletGrad,
     StokesletPressure, /* also the regularized Oseen pressure (reg, eps != 0) */
     StressletPressure,
+    Nearest, /* arg-min, not a sum: strengths {index, group}, 4-wide targets {r, group} */
 };
 
 /* Doubles per source of the strength array and per target of the output
@@ -38,6 +39,15 @@ PairDims pair_kernel_dims(PairKernel kernel);
 hipError_t launch_pair_kernel(PairKernel kernel, const double *r_src, const double *f_src,
                               const double *r_trg, double *out, long long n_src, long long n_trg,
                               double scale, double reg, double eps, hipStream_t stream);
+
+/* Per target the nearest source whose group differs from the target's (every
+ * source without groups: both group pointers null): d2[t] = min |t - s|^2 and
+ * index[t] the lowest source index that attains it, +inf and -1 without an
+ * eligible source. Device pointers, asynchronous on `stream`; every
+ * intermediate lives in the stream's launch workspace. */
+hipError_t launch_nearest(const double *r_src, const long long *src_group, long long n_src,
+                          const double *r_trg, const long long *trg_group, long long n_trg,
+                          double *d2, long long *index, hipStream_t stream);
 
 /* n_src sources as `kernel`'s packed records into `rec`, which holds
  * rec_doubles<K>() * rec_count<K>(n_src) doubles (pair_functors.hpp):

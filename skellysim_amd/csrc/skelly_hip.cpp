@@ -47,6 +47,15 @@ bool negative_size(const char *where, long long a, long long b = 0) {
     return true;
 }
 
+/* The nearest-source entry points take both group arrays or neither: one
+ * without the other is an error of the caller's, found like a negative count. */
+bool lone_group(const char *where, const void *src_group, const void *trg_group) {
+    if ((src_group == nullptr) == (trg_group == nullptr))
+        return false;
+    set_error(where, "one group array without the other");
+    return true;
+}
+
 /* Persistent per-process device state. Calls are serialized (the reference is
  * MPI_THREAD_FUNNELED, skelly_sim.cpp:14). */
 struct Context {
@@ -447,6 +456,71 @@ int skelly_oseen_contract_pressure_device(const double *d_r_src, const double *d
     return pair_device("skelly_oseen_contract_pressure_device", PairKernel::StokesletPressure,
                        d_r_src, d_density, n_src, d_r_trg, d_p_trg, n_trg, kOneOver4Pi, reg,
                        epsilon_distance, stream);
+}
+
+/* ---- nearest source: d2 and index per target (launch_nearest) ---- */
+
+int skelly_nearest_device(const double *d_r_src, const long long *d_src_group, long long n_src,
+                          const double *d_r_trg, const long long *d_trg_group, long long n_trg,
+                          double *d_d2, long long *d_index, void *stream) {
+    const char *where = "skelly_nearest_device";
+    if (negative_size(where, n_src, n_trg) || lone_group(where, d_src_group, d_trg_group))
+        return -1;
+    CHK(where, skelly::launch_nearest(d_r_src, d_src_group, n_src, d_r_trg, d_trg_group, n_trg,
+                                      d_d2, d_index, (hipStream_t)stream));
+    return 0;
+}
+
+/* Host form: one block for the call (inputs, then d2 and index), upload,
+ * launch, download, sync on the library's stream. */
+int skelly_nearest_host(const double *r_src, const long long *src_group, long long n_src,
+                        const double *r_trg, const long long *trg_group, long long n_trg,
+                        double *d2, long long *index) {
+    const char *where = "skelly_nearest_host";
+    if (negative_size(where, n_src, n_trg) || lone_group(where, src_group, trg_group))
+        return -1;
+    if (n_trg == 0)
+        return 0;
+    const bool grouped = src_group != nullptr;
+    const size_t ns = (size_t)n_src, nt = (size_t)n_trg;
+    /* all items are 8 bytes wide */
+    const size_t words = ns * 3 + nt * 3 + (grouped ? ns + nt : 0) + nt * 2;
+    Context &c = ctx();
+    std::lock_guard<std::mutex> lock(c.mu);
+    CHK(where, c.ensure_stream());
+    double *block = nullptr;
+    CHK(where, hipMalloc((void **)&block, words * 8));
+    /* everything below frees the block on its way out */
+    hipError_t err = hipSuccess;
+    double *at = block;
+    auto upload = [&](const void *p, size_t n) {
+        double *dst = at;
+        if (n && err == hipSuccess)
+            err = hipMemcpyAsync(dst, p, n * 8, hipMemcpyHostToDevice, c.stream);
+        at += n;
+        return dst;
+    };
+    const double *d_rs = upload(r_src, ns * 3);
+    const double *d_rt = upload(r_trg, nt * 3);
+    const long long *d_sg = nullptr, *d_tg = nullptr;
+    if (grouped) {
+        d_sg = reinterpret_cast<const long long *>(upload(src_group, ns));
+        d_tg = reinterpret_cast<const long long *>(upload(trg_group, nt));
+    }
+    double *d_d2 = at;
+    long long *d_index = reinterpret_cast<long long *>(at + nt);
+    if (err == hipSuccess)
+        err = skelly::launch_nearest(d_rs, d_sg, n_src, d_rt, d_tg, n_trg, d_d2, d_index,
+                                     c.stream);
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(d2, d_d2, nt * 8, hipMemcpyDeviceToHost, c.stream);
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(index, d_index, nt * 8, hipMemcpyDeviceToHost, c.stream);
+    const hipError_t sync = hipStreamSynchronize(c.stream);
+    (void)hipFree(block);
+    CHK(where, err);
+    CHK(where, sync);
+    return 0;
 }
 
 /* stresslet x normal x density: the prefactor -3/(4*pi) is the functor's own

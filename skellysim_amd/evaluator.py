@@ -176,6 +176,45 @@ def oseen_contract_pressure(r_src, r_trg, density, reg=5e-3, epsilon_distance=1e
     return _host_pair(_OSEEN_PRESSURE, r_src, density, r_trg, (reg, epsilon_distance))
 
 
+# Nearest source, host arrays. Not a sum: per target the smallest squared
+# distance to an eligible source and the index of that source (the lowest
+# among equals); +inf and -1 where there is none. With groups a source is
+# eligible when its group id differs from the target's.
+
+def _groups(src_group, trg_group, n_src, n_trg, convert):
+    """Both group arrays as `convert` makes them, or (None, None): the library
+    takes both or neither."""
+    if (src_group is None) != (trg_group is None):
+        raise ValueError("src_group and trg_group: pass both or neither")
+    if src_group is None:
+        return None, None
+    sg, tg = convert(src_group, "src_group"), convert(trg_group, "trg_group")
+    _same_length(sg.shape[0], "src_group", n_src, "r_src")
+    _same_length(tg.shape[0], "trg_group", n_trg, "r_trg")
+    return sg, tg
+
+
+def _host_group(g, name):
+    g = np.ascontiguousarray(np.asarray(g).reshape(-1))
+    if g.dtype.kind not in "iu":
+        raise TypeError(f"{name}: expected integer group ids, got {g.dtype}")
+    return g.astype(np.int64, copy=False)
+
+
+def nearest(r_src, r_trg, src_group=None, trg_group=None):
+    """(d2 float64 (n_trg,), index int64 (n_trg,)) of skelly_nearest_host
+    (include/skelly_hip.h states the tie, +inf / -1 and NaN rules)."""
+    src, trg = _rows(r_src, 3, "r_src"), _rows(r_trg, 3, "r_trg")
+    sg, tg = _groups(src_group, trg_group, len(src), len(trg), _host_group)
+    d2 = np.empty(len(trg))
+    index = np.empty(len(trg), dtype=np.int64)
+    ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    rc = _native.lib().skelly_nearest_host(ptr(src), ptr(sg), len(src), ptr(trg), ptr(tg),
+                                           len(trg), ptr(d2), ptr(index))
+    _native.check(rc, "nearest")
+    return d2, index
+
+
 class Evaluator:
     """Callable mirroring kernels::Evaluator for one kernel type."""
 
@@ -184,6 +223,10 @@ class Evaluator:
 
     def __call__(self, r_sl, r_dl, r_trg, f_sl, f_dl, eta):
         return self._fn(r_sl, r_dl, r_trg, f_sl, f_dl, eta)
+
+    # the nearest-source search is no kernel type of the reference's: every
+    # evaluator offers the one host form
+    nearest = staticmethod(nearest)
 
 
 def set_evaluator(name):
@@ -395,6 +438,40 @@ def oseen_contract_pressure_device(r_src, r_trg, density, reg=5e-3, epsilon_dist
                                    out=None):
     """Pressure of oseen_contract_device's field."""
     return _device_pair(_OSEEN_PRESSURE, r_src, density, r_trg, out, (reg, epsilon_distance))
+
+
+# ---------------------------------------------------------------------------
+# nearest source on device tensors
+# ---------------------------------------------------------------------------
+
+def _dev_group(g, name):
+    import torch
+    if not (isinstance(g, torch.Tensor) and g.is_cuda):
+        raise TypeError(f"{name}: expected a CUDA torch tensor (no CPU fallback)")
+    if g.dtype != torch.int64:
+        raise TypeError(f"{name}: expected int64, got {g.dtype}")
+    if g.dim() != 1:
+        raise ValueError(f"{name}: expected (n,), got {tuple(g.shape)}")
+    return g.contiguous()
+
+
+def nearest_device(r_src, r_trg, src_group=None, trg_group=None):
+    """nearest() on device tensors: (d2 float64 (n_trg,), index int64
+    (n_trg,)), asynchronous on torch's current stream. Groups are int64
+    tensors (n,), both or neither."""
+    import torch
+    r_src = _dev_rows(r_src, 3, "r_src")
+    r_trg = _dev_rows(r_trg, 3, "r_trg")
+    sg, tg = _groups(src_group, trg_group, r_src.shape[0], r_trg.shape[0], _dev_group)
+    n_trg = r_trg.shape[0]
+    d2 = torch.empty((n_trg,), dtype=torch.float64, device=r_trg.device)
+    index = torch.empty((n_trg,), dtype=torch.int64, device=r_trg.device)
+    ptr = lambda t: None if t is None else _dptr(t)
+    rc = _native.lib().skelly_nearest_device(_dptr(r_src), ptr(sg), r_src.shape[0], _dptr(r_trg),
+                                             ptr(tg), n_trg, _dptr(d2), _dptr(index),
+                                             _stream_ptr())
+    _native.check(rc, "nearest_device")
+    return d2, index
 
 
 # ---------------------------------------------------------------------------

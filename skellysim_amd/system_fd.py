@@ -121,6 +121,21 @@ class HipBackend:
     def oseen_contract_pressure(self, r_src, r_trg, density):
         return self._eval("oseen_contract_pressure", (r_src, r_trg, density))
 
+    def nearest(self, r_src, r_trg, src_group=None, trg_group=None):
+        """(d2, index) of evaluator.nearest_device on this device: per target
+        the nearest source whose group differs from its own (every source
+        without groups). Tensors (asynchronous) when r_src is one, else numpy."""
+        import torch
+        from . import evaluator
+        groups = [None if g is None else
+                  (g.to(self.dev) if torch.is_tensor(g) else
+                   torch.from_numpy(np.ascontiguousarray(g, dtype=np.int64)).to(self.dev))
+                  for g in (src_group, trg_group)]
+        d2, index = evaluator.nearest_device(self._t(r_src), self._t(r_trg), *groups)
+        if torch.is_tensor(r_src):
+            return d2, index
+        return d2.cpu().numpy(), index.cpu().numpy()
+
     def trace_streamlines(self, seeds, eta, stokeslet=None, stresslet=None, rotlet=None,
                           oseen=None, background=None, bodies=None, **control):
         """evaluator.trace_streamlines_device on this device: the source sets
@@ -202,8 +217,12 @@ class SystemFD:
         self.motor_activation_delay = 0.0
         self.background_flow = background_flow  # fn: (n,3) -> (n,3)
         # steric fiber-periphery repulsion (system.cpp:421, params.cpp:18):
-        # dict(kind="sphere"|"ellipsoid", f_0=, l_0=, radius=|abc=) or None
+        # dict(kind="sphere"|"ellipsoid", f_0=, l_0=, radius=|abc=) or None.
+        # ENGINE EXTENSION: kind="generic" with nodes=, normals= (default:
+        # this system's shell), for both dicts — contact.py
         self.periphery_interaction = periphery_interaction
+        # (n_fiber_nodes, 3) periphery force of the last prep
+        self.periphery_force = None
         self.backend = backend if backend is not None else HipBackend()
         self._uniform = self._fibers_uniform()
 
@@ -429,9 +448,13 @@ class SystemFD:
         # periphery binding re-evaluates the plus-end BCs every prep
         # (fc_->update_boundary_conditions, system.cpp:453)
         if self.periphery_binding and self.periphery_binding.get("active"):
+            # a generic shell binds nothing, as the reference's stub
+            # (GenericPeriphery::check_collision, periphery.cpp:264-335)
+            shape = self.periphery_shape
+            if shape is not None and shape["kind"] == "generic":
+                shape = None
             for f in self.fibers:
-                f.update_boundary_conditions(self.periphery_shape,
-                                             self.periphery_binding)
+                f.update_boundary_conditions(shape, self.periphery_binding)
         if not (self._uniform and self.fibers):
             for f in self.fibers:
                 f.update_linear_operator(dt, eta)
@@ -457,8 +480,16 @@ class SystemFD:
         ext = np.zeros((nf_nodes, 3))
         if self.periphery_interaction is not None:
             pi = self.periphery_interaction
-            for f, a, b in self._fiber_node_slices():
-                ext[a:b] = f.periphery_repulsion(**pi).T
+            if pi["kind"] == "generic":
+                # ENGINE EXTENSION: every fiber node against the shell's
+                # nodes in one nearest-source launch (contact.py)
+                if nf_nodes:
+                    ext[:] = self._generic_periphery_force(pi)
+            else:
+                for f, a, b in self._fiber_node_slices():
+                    ext[a:b] = f.periphery_repulsion(**pi).T
+        # what the periphery alone exerts, for inspection
+        self.periphery_force = ext.copy()
         # fiber-fiber steric repulsion (ENGINE EXTENSION, opt-in; see
         # _fiber_fiber_repulsion)
         if self.steric_interaction is not None and nf_nodes:
@@ -860,6 +891,76 @@ class SystemFD:
         np.add.at(out, j, -fvec)
         return out
 
+    # ---- generic-periphery contact (ENGINE EXTENSION, contact.py) --------
+    def _generic_shell(self, spec):
+        """(nodes, normals) of a kind="generic" periphery dict: its own
+        nodes= / normals=, by default the system's shell."""
+        nodes, normals = spec.get("nodes"), spec.get("normals")
+        if nodes is None or normals is None:
+            if self.shell is None:
+                raise ValueError('periphery kind "generic" needs nodes= and '
+                                 "normals=, or a system with a shell")
+            nodes, normals = self.shell.nodes, self.shell.normals
+        return nodes, normals
+
+    def _free_fiber_nodes(self):
+        """Mask over fiber_nodes() of the nodes that take part in periphery
+        contact: all but node 0 of minus-clamped fibers (periphery.cpp:148,
+        f_c_fd.cpp:39-55)."""
+        free = np.ones(self.fiber_node_count, dtype=bool)
+        for f, a, _ in self._fiber_node_slices():
+            if f.minus_clamped:
+                free[a] = False
+        return free
+
+    def _generic_periphery_force(self, pi):
+        """(n_fiber_nodes, 3) force of a generic shell on all fiber nodes, one
+        launch; node 0 of minus-clamped fibers gets none, as in the other
+        kinds."""
+        from .contact import generic_periphery_force
+        nodes, normals = self._generic_shell(pi)
+        f = generic_periphery_force(self.fiber_nodes(), nodes, normals,
+                                    pi.get("f_0", 20.0), pi.get("l_0", 0.05),
+                                    self.backend)
+        f[~self._free_fiber_nodes()] = 0.0
+        return f
+
+    def _generic_collision(self, shape, threshold):
+        """check_collision against a generic shell: the fiber nodes (without
+        node 0 of minus-clamped fibers) and the centres of the spherical
+        bodies in one launch. A node collides when gap <= threshold, a
+        spherical body when gap(centre) - R_body <= threshold (the generic
+        counterpart of periphery.cpp:94-97); ellipsoidal bodies are a no-op
+        as in the other kinds."""
+        from .contact import shell_gap
+        from .body import EllipsoidalBody
+        nodes, normals = self._generic_shell(shape)
+        pts = self.fiber_nodes()[self._free_fiber_nodes()]
+        spheres = [b for b in self.bodies if not isinstance(b, EllipsoidalBody)]
+        margin = np.concatenate([np.zeros(len(pts)),
+                                 np.array([b.radius for b in spheres], dtype=float)])
+        if not len(margin):
+            return False
+        centres = np.array([b.position for b in spheres], dtype=float).reshape(-1, 3)
+        gap, _ = shell_gap(np.concatenate([pts, centres]), nodes, normals, self.backend)
+        return bool(np.any(gap - margin <= threshold))
+
+    def min_fiber_gap(self):
+        """(distance, (fiber_i, node_i), (fiber_j, node_j)): the closest pair
+        of nodes on two different fibers, from one grouped nearest-source
+        launch over all fiber nodes (group = fiber). A diagnostic: no force
+        depends on it. (inf, None, None) with fewer than two fibers."""
+        from .contact import min_group_gap
+        fid = np.concatenate([np.full(f.n_nodes, i, dtype=np.int64)
+                              for i, f in enumerate(self.fibers)]) \
+            if self.fibers else np.zeros(0, dtype=np.int64)
+        d, i, j = min_group_gap(self.fiber_nodes(), fid, self.backend)
+        if i < 0:
+            return d, None, None
+        start = np.cumsum([0] + [f.n_nodes for f in self.fibers])
+        where = lambda k: (int(fid[k]), int(k - start[fid[k]]))
+        return d, where(i), where(j)
+
     def repin_to_bodies(self):
         """Translate every body-attached fiber so its minus end coincides
         with the body's nucleation site again — fiber and body do not move
@@ -891,7 +992,10 @@ class SystemFD:
         periphery_interaction."""
         from .fiber_fd import points_collide
         from .body import EllipsoidalBody
-        if periphery_shape is not None:
+        if periphery_shape is not None and periphery_shape["kind"] == "generic":
+            if self._generic_collision(periphery_shape, threshold):
+                return True
+        elif periphery_shape is not None:
             for f in self.fibers:
                 pc = f.x[:, 1:] if f.minus_clamped else f.x
                 if points_collide(pc, periphery_shape, threshold):
